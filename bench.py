@@ -12,16 +12,24 @@ value (SURVEY §8d timing rule, BAM in -> BAM out, BGZF at -c 6): one step is th
 GPU deflate, EOF block; the output BAM file ends in HBM).  The input file is made once before the
 timed region by the library's own GPU deflate from the device generator.  The GPU deflate is a greedy
 single-candidate parse (DEFLATE_SEARCH below), not zlib's level-6 lazy hash-chain search: its output is
-~3% larger; config.deflate carries both ratios.
+~3% larger; config.deflate carries both ratios (zlib's under --full).
 
-Also on the same JSON line:
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what `value` needs: it generates the
+records and the input file, warms up, times the N steps, writes --dump-outputs DIR if given and prints
+the JSON line with the steps' own stage times and the roofline figures derived from them (no runs of
+their own).  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (dump_outputs:
+the counts and a fixed, seeded sample of the output file's bytes); the generator and the GPU deflate are
+deterministic, so the same arguments give the same input file in every run.
+
+With --full, also on the same JSON line:
   kernel_step   -- the sort+dedup device pipeline alone over records already decoded in HBM
                    (oge_sort_markdup_dev), the round-1 headline, with its stage times
   pcie_inclusive-- the same chain from a BAM file in page-locked host memory to one in host memory
                    (oge_mergesort_bgzf_host: upload overlapped with the framing index and inflate, the
                    download with the deflate), second call timed, the first reported (never `value`)
-  roofline      -- the e2e step's dominant kernel: algorithmic bytes per launch / its HIP-event time
-                   (events on the context stream), traffic from the committed rocprofv3 PMC summary
+  roofline      -- (a plain run has it too) the e2e step's dominant kernel: algorithmic bytes per launch /
+                   its HIP-event time (events on the context stream), traffic from the committed rocprofv3
+                   PMC summary
   cpu_baseline  -- the REFERENCE itself (oracle/_ref/ref_driver: OpenGE's own ReadSorter +
                    MarkDuplicates + BamSerializer modules compiled from its sources here, the
                    mergesort -M --nosplit chain with -v) timed on this box's host cores on a bounded
@@ -34,7 +42,8 @@ range (block and record boundaries joined with the neighbouring ranks), range-sp
 keys with sampled splitters, exchanges the records with an all-to-all (RCCL over xGMI between GPUs; the
 host-staged transport when ranks share a GPU), sorts each rank's slice and marks duplicates exactly
 with hash-routed mate-join / pair-group exchanges.  value = reads / max-over-ranks wall
-time.  --dump-dir writes every rank's output slice (tests/test_gpu_multiproc.py concatenates them).
+time.  --dump-dir writes every rank's output slice (tests/test_gpu_multiproc.py concatenates them);
+the realign leg over the ranks runs under --full.
 """
 from __future__ import annotations
 
@@ -73,6 +82,11 @@ def parse():
     ap.add_argument("--pairs", type=int, default=150_000_000, help="read pairs (default 150M = 300M reads)")
     ap.add_argument("--seed", type=int, default=1234, help="C2 generator seed")
     ap.add_argument("--dump-dir", default=None, help="multi-GPU: write each rank's output slice here (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every leg beside the headline steps: realign (C5), kernel-only step, in-place dedup, "
+                         "zlib-6 and level-9 deflate ratios, PCIe-inclusive run, CPU baselines (off: only the steps)")
     ap.add_argument("--level", type=int, default=6, help="BGZF level of the input file and of the output")
     ap.add_argument("--kernel-steps", type=int, default=3, help="timed steps of the kernel-only leg")
     ap.add_argument("--cpu-sample-reads", type=int, default=2_000_000)
@@ -84,7 +98,10 @@ def parse():
     ap.add_argument("--realign-only", action="store_true", help="profiling aid: only the C5 realign leg")
     ap.add_argument("--e2e-only", action="store_true", help="profiling aid: skip every leg but the e2e steps")
     ap.add_argument("--kernel-only", action="store_true", help="profiling aid: only the kernel-only leg")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if (args.realign_only or args.kernel_only) and not args.full:
+        ap.error("--realign-only / --kernel-only select a leg of --full: add --full")
+    return args
 
 
 def log(msg: str) -> None:
@@ -158,6 +175,38 @@ def stage_ms(ctx, names) -> dict:
         if v >= 0:
             out[s] = v
     return out
+
+
+DUMP_CHUNK = 4096   # bytes per sampled piece of the output file
+DUMP_CHUNKS = 2048  # pieces: 8 MiB of file bytes = 32 MiB as float32
+
+
+def dump_outputs(directory: str, ctx, L, d_out: int, out_bytes: int, nr: int, nd: int, seed: int, tag: str = "") -> None:
+    """--dump-outputs: what the last timed step returned to its caller, as .npy files two builds can be
+    compared by.  counts<tag>.npy (float64): output file bytes, records written, duplicates flagged.
+    output_file_sample<tag>.npy (float32, DUMP_CHUNKS x DUMP_CHUNK): bytes of the output BAM file in HBM --
+    the whole file when it fits, else its first and last piece and pieces drawn by a generator seeded
+    with --seed (the same pieces in every run of the same arguments; a short last piece is zero-padded).
+    sample_offsets<tag>.npy (float64): the file offset of every row."""
+    import numpy as np
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    npieces = max(1, -(-out_bytes // DUMP_CHUNK))
+    if npieces <= DUMP_CHUNKS:
+        idx = np.arange(npieces, dtype=np.int64)
+    else:
+        rng = np.random.default_rng(seed)
+        mid = rng.choice(npieces - 2, size=DUMP_CHUNKS - 2, replace=False).astype(np.int64) + 1
+        idx = np.sort(np.concatenate([np.array([0, npieces - 1], np.int64), mid]))
+    rows = np.zeros((len(idx), DUMP_CHUNK), np.uint8)
+    for r, i in enumerate(idx):
+        off = int(i) * DUMP_CHUNK
+        nb = min(DUMP_CHUNK, out_bytes - off)
+        if nb > 0:
+            L.check(L.lib().oge_memcpy(ctx.h, rows[r].ctypes.data, d_out + off, nb, 2), ctx.h)
+    np.save(d / f"counts{tag}.npy", np.array([out_bytes, nr, nd], np.float64))
+    np.save(d / f"output_file_sample{tag}.npy", rows.astype(np.float32))
+    np.save(d / f"sample_offsets{tag}.npy", (idx * DUMP_CHUNK).astype(np.float64))
 
 
 def pmc_files() -> list:
@@ -590,7 +639,7 @@ def main():
     #      first realigner call of a fresh process, as in `openge localrealign`, not one that follows the 300M
     #      legs' host-memory churn (the pinned 60 + 57 GB of the PCIe leg)
     realign_res = None
-    if not args.no_realign and not args.e2e_only and not args.kernel_only:
+    if args.full and not args.no_realign and not args.e2e_only and not args.kernel_only:
         log("realign leg")
         rctx = L.Context(local, stream=stream.cuda_stream)
         realign_res = realign_leg(rctx, args.realign_intervals, cpu_threads=0 if args.no_cpu_baseline else args.cpu_threads)
@@ -606,7 +655,7 @@ def main():
     hb = bam_header_bytes(buf.value.decode())
     n = n_all
     kargs = argparse.Namespace(**vars(args))
-    if args.e2e_only:
+    if args.e2e_only or not args.full:
         kargs.kernel_steps = 0
     kres, S, B, hdr_text = kernel_leg(ctx, L, torch, dev, p, n, len(hb), kargs)
     log(f"kernel leg: {kres.get('ms_per_step')} ms/step; records {B / 1e9:.2f} GB")
@@ -619,8 +668,9 @@ def main():
     seq_bytes = n * ((p.read_len + 1) // 2)
 
     # ---- the input BAM file in HBM (level-6 BGZF, GPU deflate), staging freed
-    zref = zlib6_sample_ratio(S, len(hb), B)
-    chain_probe = {}
+    #      (--full: also the zlib-6 ratio of a sample and one level-9 deflate of the same bytes)
+    zref = zlib6_sample_ratio(S, len(hb), B) if args.full else None
+    chain_probe = {} if args.full else None
     d_z, zbytes = build_input(ctx, L, S, total, args.level, chain_probe)
     torch.cuda.synchronize(dev)
     log(f"input BAM file in HBM: {zbytes / 1e9:.2f} GB (ratio {zbytes / total:.3f})")
@@ -657,6 +707,8 @@ def main():
     log(f"HBM free during e2e steps {fr / 1e9:.1f} GB")
     log(f"e2e: {ms_step:.1f} ms/step = {value:.1f} Mreads/s; stages {sms}")
     assert nr == n, (nr, n)
+    if args.dump_outputs and K > 0:  # before any other call on the context: d_out is valid until the next one
+        dump_outputs(args.dump_outputs, ctx, L, d_out, out_bytes, nr, nd, args.seed)
 
     # roofline: the dominant kernel of the e2e step (bound per stage; VALU fraction for the codec)
     kinfo = stage_kernels(B, zbytes, out_bytes, n, seq_bytes)
@@ -668,7 +720,7 @@ def main():
     #      oge_mergesort_bgzf_host overlaps its upload with the framing index and inflate, and the output's
     #      download with the deflate
     pcie = None
-    if not args.no_pcie and not args.e2e_only:
+    if args.full and not args.no_pcie and not args.e2e_only:
         hz = torch.empty(zbytes, dtype=torch.uint8, pin_memory=True)
         d_z.get(0, zbytes, hz.data_ptr())
         d_z.free()
@@ -721,7 +773,7 @@ def main():
             cli_s = ((out["realign"] or {}).get("cli") or {}).get("seconds")
             if cli_s and rc_.get("seconds"):  # like for like: both whole commands, file to file, fresh processes
                 rc_["cli_speedup_file_to_file"] = round(rc_["seconds"] / cli_s, 1)
-    if not args.no_cpu_baseline and not args.e2e_only:
+    if args.full and not args.no_cpu_baseline and not args.e2e_only:
         log("cpu baseline (reference)")
         cb = cpu_baseline_reference(args.cpu_sample_reads, args.cpu_threads)
         if cb.get("value"):
@@ -837,11 +889,13 @@ def multi_gpu(args, ctx, L, torch, dist, dev, p, n_all, world, rank):
         hs = torch.empty(max(ob, 1), dtype=torch.uint8)
         L.check(L.lib().oge_memcpy(ctx.h, hs.data_ptr(), d_last, ob, 2), ctx.h)
         Path(args.dump_dir, f"slice_{rank}.bam").write_bytes(hs[:ob].numpy().tobytes())
+    if args.dump_outputs and K > 0:  # this rank's slice of the output file
+        dump_outputs(args.dump_outputs, ctx, L, d_last, ob, nr, nd, args.seed, tag=f"_rank{rank}")
     comm.close()
     d_zb.free()
     torch.cuda.empty_cache()
     realign_multi = None
-    if not args.no_realign:
+    if args.full and not args.no_realign:
         realign_multi = realign_leg(ctx, args.realign_intervals, rank, world, dump_dir=args.dump_dir)
     if rank == 0:
         out = {"metric": METRIC, "value": round(n_all * K / dt / 1e6, 2), "unit": "Mreads/s", "n_gpus": world,

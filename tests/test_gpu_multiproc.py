@@ -63,7 +63,7 @@ RL_INTERVALS = 1500  # C5 generator, small enough for 8 ranks that each generate
 def one_gpu_realign(built, tmp_path_factory):
     """bench.py's realign leg in one process (world 1) on the small C5 set: its realigned records."""
     d = tmp_path_factory.mktemp("rl1")
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--realign-only", "--realign-intervals", str(RL_INTERVALS),
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--realign-only", "--realign-intervals", str(RL_INTERVALS),
            "--no-cpu-baseline", "--dump-dir", str(d)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-4000:]
@@ -90,7 +90,7 @@ def test_bench_multiprocess_bootstrap_matches_reference(world, realign, records,
            f"--nproc-per-node={world}",
            str(ROOT / "bench.py"), "--gpus", str(world), "--pairs", "20000", "--seed", "99", "--steps", "1",
            "--warmup", "1", "--dump-dir", str(tmp_path)]
-    cmd += ["--realign-intervals", str(RL_INTERVALS)] if realign else ["--no-realign"]
+    cmd += ["--full", "--realign-intervals", str(RL_INTERVALS)] if realign else ["--no-realign"]  # the realign leg: --full
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

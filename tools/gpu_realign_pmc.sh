@@ -4,8 +4,8 @@ cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/${1:-rlpmc}
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --realign-only > $OUT/bench_rl.json 2> $OUT/bench_rl.err || { tail -20 $OUT/bench_rl.err; exit 1; }
-timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_RD --kernel-include-regex "k_planes|k_scan_bp|k_realign_scan" -d $OUT/sq -o run --output-format csv -- python3 bench.py --realign-only > $OUT/sq.json 2> $OUT/sq.err || { tail -20 $OUT/sq.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --full --realign-only > $OUT/bench_rl.json 2> $OUT/bench_rl.err || { tail -20 $OUT/bench_rl.err; exit 1; }
+timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_RD --kernel-include-regex "k_planes|k_scan_bp|k_realign_scan" -d $OUT/sq -o run --output-format csv -- python3 bench.py --full --realign-only > $OUT/sq.json 2> $OUT/sq.err || { tail -20 $OUT/sq.err; exit 1; }
 python3 - <<'PY' $OUT
 import csv, sys, json
 d = sys.argv[1]
