@@ -399,12 +399,28 @@ uint64_t oge_bgzf_bound(uint64_t n);
  * deflate, or stored blocks for level 0 / incompressible payloads) written back to back at d_dst.
  * No EOF marker is appended.  dst_cap must be >= oge_bgzf_bound(n); *out_bytes = stream size.
  * Levels 1-7: greedy one-candidate parse; 8-9: same-prefix match chains (8 / 32 deep) with lazy
- * matching, ~1 % smaller output at 1.7-3x the time.  Deterministic: the same input gives the same bytes. */
+ * matching, ~1 % smaller output at 1.7-3x the time.  Deterministic: the same input gives the same bytes.
+ * The match search is the context's (oge_ctx_set_deflate_search, below): OGE_DEFL_FAST, the default,
+ * OGE_DEFL_NEAR, OGE_DEFL_SPAN or both; level 0 and the stored-block fallback ignore it. */
 int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t n, int level, uint8_t *d_dst,
                          uint64_t dst_cap, uint64_t *out_bytes);
 /* Host-buffer form (uploads, compresses, downloads); dst_cap >= the compressed size. */
 int oge_bgzf_deflate(oge_ctx *ctx, const uint8_t *src, uint64_t n, int level, uint8_t *dst, uint64_t dst_cap,
                      uint64_t *out_bytes);
+/* The match search of oge_bgzf_deflate[_dev] and of every device writer built on it, two independent
+ * bits beside `level` (which keeps choosing depth and lazy matching):
+ *   OGE_DEFL_FAST  candidates from the earlier rounds of 1024 positions only, matches end at their
+ *                  64-byte segment's edge (the default; its bytes never change with the other modes)
+ *   OGE_DEFL_NEAR  also the earliest same-prefix position of a position's own round (the previous BAM
+ *                  record's name prefix, flags and tags are usually that near)
+ *   OGE_DEFL_SPAN  matches run across segment edges, up to 258 bytes (cut at 32 KiB sub-blocks only)
+ * On real reads NEAR | SPAN writes 14 % fewer bytes than FAST at level 6 for ~40 % more deflate
+ * time, NEAR alone 10 % fewer for ~13 % more.  A new context has OGE_DEFL_FAST unless
+ * the environment variable OGE_DEFLATE_SEARCH = fast | near | span | near+span is set when it is created
+ * (any other word fails oge_ctx_create).  set: OGE_ERR_ARG outside 0..3. */
+enum { OGE_DEFL_FAST = 0, OGE_DEFL_NEAR = 1, OGE_DEFL_SPAN = 2 };
+int oge_ctx_set_deflate_search(oge_ctx *ctx, int search);
+int oge_ctx_deflate_search(oge_ctx *ctx);
 /* ---- BGZF decompression and BAM record boundaries on the device (replaces BgzfInputStream,
  * util/bgzf_input_stream.cpp:65-142,208-240, and BamDeserializer's record walk,
  * util/bam_deserializer.h:143-193) ------------------------------------------------------ */

@@ -14,6 +14,8 @@
 //   k_defl_parse   one 512-thread workgroup per payload, the payload in LDS: hash-table match candidates
 //                  in rounds, a greedy parse of every 64-byte segment by its thread (literal runs
 //                  skipped by mask), symbol frequencies; out: per segment a literal mask + its matches.
+//   k_defl_parse_x the same outputs from the searches a caller selects (oge_ctx_set_deflate_search):
+//                  NEAR = candidates from a position's own round too, SPAN = matches across segment edges.
 //   k_defl_huff    one wave per payload: length-limited Huffman code lengths for the literal/length
 //                  (15 bits), distance (15) and code-length (7) alphabets, canonical bit-reversed
 //                  codes, the block header bit string, and the exact block size (stored or dynamic).
@@ -412,6 +414,316 @@ __global__ void __launch_bounds__(kTP) k_defl_parse(const uint8_t *__restrict__ 
 #endif
 #undef PCLK
     __syncthreads();  // the counts read out of htab before the next payload clears it
+    }
+}
+
+// ------------------------------------------------------------------------------------ parse, wider searches
+// The searches a caller asks for (oge_ctx_set_deflate_search); k_defl_parse above stays the default's.
+// On real reads the default loses most to two things: a position never sees a candidate of
+// its own round of 1024 positions (a BAM record is ~350 bytes, so the previous record's name prefix,
+// flags and tags usually sit in the same round), and every match ends at its 64-byte segment's edge.
+//   NEAR  a round-local table loc (2^11 buckets, the hash's top bits): in round g every position does
+//         atomicMax(loc[h'], (g + 1) << 10 | 1023 - (p - r)), so after the barrier the bucket holds the
+//         round's earliest position e with that bucket (the round number in the high bits: no clearing
+//         between rounds); if e < p and their 4-byte words are equal, e is p's candidate -- it is nearer
+//         than any earlier round's -- else the earlier rounds' candidate stands.  Only atomicMax: the
+//         result does not depend on scheduling.  In the chained levels cand[p] = e + 1 keeps "a candidate
+//         is a verified same-prefix predecessor".
+//   SPAN  matches run on to the sub-block's end (maxL = min(258, end - position)), so a segment's parse
+//         starts where the last match of the segments before it ended.  A thread's parse is a pure
+//         function of that entry offset (lazy matching looks at q and q + 1 only), so the entries are
+//         found by iteration: every thread parses from its segment's start and publishes E = the end of
+//         its last token; entry[t] = max(E[s], s < t) by a prefix maximum (a covered segment passes the
+//         carry on within the iteration); threads whose entry moved parse again; until no entry moves.
+//         After iteration k the segments 0..k-1 are final, so the fixpoint is the serial parse whatever the
+//         schedule, and kT + 1 iterations bound the loop for any input.  A thread's last parse is the final
+//         one, so its tokens are in place when the loop ends; the symbols are counted after it, from the
+//         final tokens only.  A covered segment has lmask = 0, nmatch = 0.
+// One hash table and two barriers per round (lookups, barrier, inserts, barrier: the r03 scheme, the same
+// candidates as the two tables above); the freed 16 KiB hold loc and the symbol counts.  LDS: 163,600 B.
+constexpr int kLocBits = 11;
+template <bool CHAIN, bool NEAR, bool SPAN>
+__global__ void __launch_bounds__(kTP) k_defl_parse_x(const uint8_t *__restrict__ src, uint64_t n, uint64_t blk0, uint64_t nb,
+                                                     uint64_t *__restrict__ lmask, uint8_t *__restrict__ nmatch,
+                                                     uint32_t *__restrict__ mlist, uint32_t *__restrict__ freq_out, int depth,
+                                                     int lazy) {
+    __shared__ __align__(16) uint32_t in[kPay / 4 + 4];
+    __shared__ uint32_t htab[1 << kHashBits];
+    __shared__ uint32_t loc[1 << kLocBits];
+    __shared__ uint32_t freq[kLitCopies + 256 * kLC];  // the fixpoint's wave maxima, then the symbol counts
+    __shared__ __align__(16) uint16_t cand[kSub];
+    static_assert(kFreq <= kLitCopies && 2 * (kT / 64) <= kLitCopies, "counts, literal copies, wave maxima and votes share freq");
+    const int t_ = threadIdx.x;
+    const bool al4 = ((uintptr_t)src & 3) == 0;
+    uint32_t pre[kPre];
+    auto fetch_or_clear = [&](uint64_t i) {  // the next payload's words (see k_defl_parse)
+        const uint64_t st0 = (blk0 + i) * kPay;
+        const uint32_t ln = i < nb ? (uint32_t)min<uint64_t>(kPay, n - st0) : 0u;
+        const OGE_G uint32_t *W = (const OGE_G uint32_t *)(src + (i < nb ? st0 : 0));
+#pragma unroll
+        for (uint32_t j = 0; j < kPre; ++j) {
+            const uint32_t k = t_ + j * kTP;
+            pre[j] = al4 && k < ln / 4 ? W[k] : 0u;
+        }
+    };
+    fetch_or_clear(blockIdx.x);
+    for (uint64_t pi = blockIdx.x; pi < nb; pi += gridDim.x) {
+    int t = t_;
+    __asm__ volatile("" : "+v"(t));  // per-payload index math stays in the loop (see k_infl_lz)
+    const int lane = t & 63, wv = t >> 6;
+    const uint64_t start = (blk0 + pi) * kPay;
+    const uint32_t len = (uint32_t)min<uint64_t>(kPay, n - start);
+    if (al4) {  // the prefetched words, then the zero-padded tail (as stage_words leaves it)
+        const uint32_t safe = len / 4, nw = (len + 3) / 4;
+#pragma unroll
+        for (uint32_t j = 0; j < kPre; ++j) {
+            const uint32_t k = t + j * kTP;
+            if (k < safe) in[k] = pre[j];
+        }
+        for (uint32_t k = safe + t; k < nw + 4; k += kTP) {
+            uint32_t v = 0;
+            if (k < nw)
+                for (int b = 0; b < 4; ++b)
+                    if (4 * k + b < len) v |= (uint32_t)src[start + 4 * k + b] << (8 * b);
+            in[k] = v;
+        }
+    } else {
+        stage_words<kTP>(in, src + start, len, t);
+    }
+    for (int i = t; i < 1 << kHashBits; i += kTP) htab[i] = 0;
+    for (int i = t; i < 1 << kLocBits; i += kTP) loc[i] = 0;  // the previous payload's round numbers
+    __syncthreads();
+
+    uint32_t g = 0;
+    uint32_t fsum = 0;  // symbol t's count over the sub-blocks
+    const uint64_t seg_base = pi * kNSeg;
+    for (int sub = 0; sub < kNSub; ++sub) {
+        const uint32_t base = sub * kSub;
+        const uint64_t sg = seg_base + (uint64_t)sub * kT + t;  // this thread's segment, stream order
+        if (base >= len) {
+            if (t < kT) lmask[sg] = 0, nmatch[sg] = 0;
+            continue;
+        }
+        const uint32_t end = min(len, base + kSub);
+        for (uint32_t r = base; r < end; r += kR * kTP, ++g) {
+            uint32_t hh[kR], cc[kR], ww[kR];
+#pragma unroll
+            for (int k = 0; k < kR; ++k) {
+                const uint32_t p = r + k * kTP + t;
+                uint32_t h = 0, c = 0, w = 0;
+                if (p + 4 <= len) {
+                    // bucket, tag and entry formats as in k_defl_parse
+                    w = ld32(in, p);
+                    const uint32_t x = w * 2654435761u, tg = CHAIN ? 0u : (x >> 5) & 0x7fffu;
+                    h = x >> (32 - kHashBits);
+                    const uint32_t e = htab[h], j1 = CHAIN ? e : e >> 15;
+                    if (j1 && p - (j1 - 1) <= 32768 && (CHAIN ? ld32(in, j1 - 1) == w : (e & 0x7fffu) == tg)) c = j1;
+                    if (NEAR) atomicMax(&loc[x >> (32 - kLocBits)], ((g + 1) << 10) | (1023u - (p - r)));
+                    h |= tg << 16;
+                }
+                hh[k] = h;
+                cc[k] = c;
+                ww[k] = w;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < kR; ++k) {
+                const uint32_t p = r + k * kTP + t;
+                const bool ok = p + 4 <= len;
+                const uint32_t hb = hh[k] & 0xffffu;
+                if (NEAR && ok) {
+                    // p's own key is in the bucket, so its maximum is this round's: the earliest position
+                    const uint32_t e = r + 1023u - (loc[hb >> (kHashBits - kLocBits)] & 1023u);
+                    if (e < p && ld32(in, e) == ww[k]) cc[k] = e + 1;
+                }
+                if (p < end) cand[p - base] = (uint16_t)cc[k];
+                if (ok && p < end) atomicMax(&htab[hb], CHAIN ? p + 1 : ((p + 1) << 15) | (hh[k] >> 16));
+            }
+            __syncthreads();
+        }
+        if (sub == kNSub - 1 || base + kSub >= len) fetch_or_clear(pi + gridDim.x);  // under the last parse
+        const uint32_t s0 = base + t * kSeg, s1 = min(end, s0 + kSeg);
+        const bool seg = t < kT && s0 < s1;
+        const uint32_t sl = seg ? s1 - s0 : 0u;
+        uint64_t cm = 0;  // the segment's candidate mask, from its 64 cand entries (eight 16-byte reads)
+        if (seg) {
+            const uint4 *cv = (const uint4 *)(cand + (s0 - base));
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const uint4 v = cv[q];
+                const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int i = 0; i < 8; ++i) cm |= (uint64_t)(((vv[i >> 1] >> (16 * (i & 1))) & 0xffff) != 0) << (8 * q + i);
+            }
+            cm &= bits_below(sl);
+        }
+        uint32_t *mp = mlist + (pi * kMaxM) * kNSeg + (uint64_t)sub * kT + t;
+        auto ext = [&](uint32_t pq, uint32_t j, uint32_t maxL) {  // as in k_defl_parse
+            uint32_t L = min(4u, maxL);
+            while (L < maxL) {
+                const uint32_t x0 = ld32(in, pq + L) ^ ld32(in, j + L);
+                const uint32_t x1 = ld32(in, pq + L + 4) ^ ld32(in, j + L + 4);
+                if (x0) {
+                    L += __builtin_ctz(x0) >> 3;
+                    break;
+                }
+                if (x1) {
+                    L += 4 + (__builtin_ctz(x1) >> 3);
+                    break;
+                }
+                L += 8;
+            }
+            return min(L, maxL);
+        };
+        // the best match at payload position pq (a candidate position), as in k_defl_parse; SPAN: up to the
+        // sub-block's end, not the segment's
+        auto best = [&](uint32_t pq, uint32_t *jo) {
+            const uint32_t maxL = min(258u, (SPAN ? end : s1) - pq);
+            uint32_t j = cand[pq - base] - 1;
+            if (!CHAIN && ld32(in, pq) != ld32(in, j)) {  // a tag collision: no candidate (a literal)
+                *jo = j;
+                return 0u;
+            }
+            uint32_t L = ext(pq, j, maxL), bj = j;
+            for (int d = 1; CHAIN && d < depth && L < maxL; ++d) {
+                if (j < base) break;
+                const uint32_t nx = cand[j - base];
+                if (!nx || pq - (nx - 1) > 32768) break;
+                j = nx - 1;
+                const uint32_t Lj = ext(pq, j, maxL);
+                if (Lj > L) L = Lj, bj = j;
+            }
+            *jo = bj;
+            return L;
+        };
+        // Parse of the segment from offset p0 < sl: the tokens go to lit, nm and mlist; returns the offset at
+        // which the last token ends (>= sl, beyond it when a match runs on).  count: the matches' symbols are
+        // counted on the way (without SPAN, where the one parse is the final one).
+        // At most kMaxM matches start in a segment: uncut, a match is >= 4 bytes long (its candidate shares
+        // a 4-byte prefix), and a cut one (the segment's edge, or with SPAN the sub-block's end) is >= 3 and
+        // the segment's last -- so the starts are >= 3 apart in either case.
+        static_assert(kMaxM * 3 >= kSeg - 1, "match starts 3 apart fill mlist exactly");
+        uint64_t lit = 0;
+        uint32_t nm = 0;
+        auto count_match = [&](uint32_t L, uint32_t d) {
+            uint32_t sym, xb, ev, dsym, dnb, dev;
+            len_code(L, sym, xb, ev);
+            dist_code(d, dsym, dnb, dev);
+            atomicAdd(&freq[sym], 1u);
+            atomicAdd(&freq[kLit + dsym], 1u);
+        };
+        auto parse = [&](uint32_t p0, const bool count) {
+            lit = 0, nm = 0;
+            uint32_t p = p0;
+            while (p < sl) {
+                const uint64_t m = cm & ~bits_below(p);
+                const uint32_t q = m ? (uint32_t)__builtin_ctzll(m) : sl;
+                lit |= bits_below(q) & ~bits_below(p);  // literals [p, q)
+                if (q >= sl) return sl;
+                const uint32_t pq = s0 + q;
+                uint32_t j;
+                const uint32_t L = best(pq, &j);
+                if (CHAIN && lazy && L >= 3 && L < 32 &&
+                    (SPAN ? pq + 1 < end && cand[pq + 1 - base] != 0 : q + 1 < sl && ((cm >> (q + 1)) & 1))) {
+                    uint32_t j1;
+                    if (best(pq + 1, &j1) > L) {  // a literal here, the longer match from the next position
+                        lit |= 1ull << q;
+                        p = q + 1;
+                        continue;
+                    }
+                }
+                if (L >= 3) {
+                    const uint32_t d = pq - j;
+                    if (count) count_match(L, d);
+                    if (nm < (uint32_t)kMaxM) mp[(uint64_t)nm * kNSeg] = (q << 23) | ((L - 3) << 15) | (d - 1);
+                    ++nm;
+                    p = q + L;
+                } else {
+                    lit |= 1ull << q;
+                    p = q + 1;
+                }
+            }
+            return p;
+        };
+        if (SPAN) {
+            // A thread parses again whenever its entry moves, so its last parse is the final one: the tokens
+            // in mlist (a later parse overwrites an earlier one's), lit and nm are the final parse's when the
+            // loop ends.  The symbols are counted after it, from those tokens.
+            uint32_t entry = s0;  // where this segment's parse starts (absolute)
+            uint32_t E = 0;       // the end of this segment's last token (absolute; 0: covered, no token)
+            bool moved = seg;
+            for (int it = 0; it <= kT; ++it) {  // segments 0..it-1 are final after iteration it
+                if (moved) {
+                    lit = 0, nm = 0, E = 0;
+                    if (entry - s0 < sl) E = s0 + parse(entry - s0, false);
+                }
+                uint32_t v = E;  // inclusive prefix maximum over the wave's segments
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const uint32_t y = __shfl_up(v, o, 64);
+                    if (lane >= o) v = max(v, y);
+                }
+                if (lane == 63 && wv < kT / 64) freq[wv] = v;
+                __syncthreads();
+                uint32_t ex = __shfl_up(v, 1, 64);
+                if (lane == 0) ex = 0;
+                for (int q = 0; q < min(wv, kT / 64); ++q) ex = max(ex, freq[q]);
+                ex = max(ex, s0);
+                moved = seg && ex != entry;
+                if (seg) entry = ex;
+                // "any entry moved", through LDS: every thread reads the same eight words, so the trip
+                // count is uniform (the wave maxima are rewritten only after this barrier, the votes only
+                // after the next iteration's first one)
+                const bool wany = __ballot(moved) != 0;
+                if (lane == 0 && wv < kT / 64) freq[kT / 64 + wv] = wany;
+                __syncthreads();
+                uint32_t any = 0;
+#pragma unroll
+                for (int q = 0; q < kT / 64; ++q) any |= freq[kT / 64 + q];
+                if (!any) break;
+            }
+        }
+        // the symbol counts of this sub-block
+        for (int i = t; i < kFreq; i += kTP) freq[i] = 0;
+        if (!CHAIN)
+            for (int i = t; i < 256 * kLC; i += kTP) freq[kLitCopies + i] = 0;
+        __syncthreads();
+        if (seg) {
+            if (SPAN) {
+                for (uint32_t k = 0; k < min(nm, (uint32_t)kMaxM); ++k) {
+                    const uint32_t tok = mp[(uint64_t)k * kNSeg];  // this thread's own stores
+                    count_match(((tok >> 15) & 255) + 3, (tok & 0x7fff) + 1);
+                }
+            } else {
+                parse(0, true);
+            }
+            // literal frequencies: the segment's 64 bytes in four 16-byte LDS reads
+            const uint4 *v4 = (const uint4 *)(in + s0 / 4);
+#pragma unroll
+            for (int w4 = 0; w4 < 4; ++w4) {
+                const uint4 v = v4[w4];
+                const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if ((lit >> (16 * w4 + k)) & 1) {
+                        const uint32_t b = (vv[k >> 2] >> (8 * (k & 3))) & 0xff;
+                        atomicAdd(&freq[CHAIN ? b : kLitCopies + b * kLC + (t & (kLC - 1))], 1u);
+                    }
+            }
+        }
+        if (t < kT) lmask[sg] = lit, nmatch[sg] = (uint8_t)nm;
+        __syncthreads();  // cand and the counts are reused by the next sub-block
+        if (t < kFreq) {
+            uint32_t c = freq[t];
+            if (!CHAIN && t < 256)  // the literal copies folded into the counts
+#pragma unroll
+                for (int q = 0; q < kLC; ++q) c += freq[kLitCopies + t * kLC + q];
+            fsum += c;
+        }
+        __syncthreads();
+    }
+    static_assert(kFreq <= kTP, "one count per thread");
+    if (t < kFreq) freq_out[pi * kFreq + t] = fsum;
     }
 }
 
@@ -1302,6 +1614,8 @@ extern "C" int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t
     if (level < 0 || level > 9) return oge_fail(ctx, OGE_ERR_ARG, "level must be 0..9");
     // levels 1-7: the greedy one-candidate parse; 8 / 9: same-prefix chains 8 / 32 deep and lazy matching
     const int depth = level >= 9 ? 32 : level == 8 ? 8 : 1, lazy = level >= 8 ? 1 : 0;
+    // the context's search (oge_ctx_set_deflate_search); level 0 writes stored blocks whatever the parse finds
+    const int search = level == 0 ? OGE_DEFL_FAST : ctx->deflate_search;
     if (dst_cap < oge_bgzf_bound(n)) return oge_fail(ctx, OGE_ERR_ARG, "dst_cap < oge_bgzf_bound(n)");
     hipSetDevice(ctx->device);
     ctx->reset_timing();
@@ -1393,12 +1707,20 @@ extern "C" int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t
     for (uint64_t b0 = 0; b0 < nblk; b0 += chunk, ++k) {
         const uint32_t nb = (uint32_t)std::min(chunk, nblk - b0);
         Bufs &u = B[k % S];
-        if (depth > 1)
-            k_defl_parse<true><<<(uint32_t)std::min<uint64_t>(nb, (uint64_t)ncu), kTP, 0, u.st>>>(d_src, n, b0, nb, u.lmask, u.nmatch,
-                                                                                            u.mlist, u.freq, depth, lazy);
+        const uint32_t pg = (uint32_t)std::min<uint64_t>(nb, (uint64_t)ncu);
+#define OGE_PARSE_X(C, N, S) \
+    k_defl_parse_x<C, N, S><<<pg, kTP, 0, u.st>>>(d_src, n, b0, nb, u.lmask, u.nmatch, u.mlist, u.freq, depth, lazy)
+        if (search == OGE_DEFL_FAST && depth > 1)
+            k_defl_parse<true><<<pg, kTP, 0, u.st>>>(d_src, n, b0, nb, u.lmask, u.nmatch, u.mlist, u.freq, depth, lazy);
+        else if (search == OGE_DEFL_FAST)
+            k_defl_parse<false><<<pg, kTP, 0, u.st>>>(d_src, n, b0, nb, u.lmask, u.nmatch, u.mlist, u.freq, 1, 0);
+        else if (search == OGE_DEFL_NEAR)
+            depth > 1 ? OGE_PARSE_X(true, true, false) : OGE_PARSE_X(false, true, false);
+        else if (search == OGE_DEFL_SPAN)
+            depth > 1 ? OGE_PARSE_X(true, false, true) : OGE_PARSE_X(false, false, true);
         else
-            k_defl_parse<false><<<(uint32_t)std::min<uint64_t>(nb, (uint64_t)ncu), kTP, 0, u.st>>>(d_src, n, b0, nb, u.lmask, u.nmatch,
-                                                                                             u.mlist, u.freq, 1, 0);
+            depth > 1 ? OGE_PARSE_X(true, true, true) : OGE_PARSE_X(false, true, true);
+#undef OGE_PARSE_X
         OGE_LAUNCH_CHECK(ctx);
         k_defl_huff<<<nb, 64, 0, u.st>>>(u.freq, u.tabs, n, b0, level, u.sizes);
         OGE_LAUNCH_CHECK(ctx);

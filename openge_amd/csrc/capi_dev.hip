@@ -169,8 +169,19 @@ int oge_ctx_create(int device, oge_ctx **out) {
     if (device < 0 || device >= ndev) return oge_fail(nullptr, OGE_ERR_ARG, "oge_ctx_create: bad device index");
     e = hipSetDevice(device);
     if (e != hipSuccess) return oge_fail(nullptr, OGE_ERR_HIP, hipGetErrorString(e));
+    int search = OGE_DEFL_FAST;
+    if (const char *w = getenv("OGE_DEFLATE_SEARCH")) {  // an unknown word is an error, not the default
+        static const char *const names[] = {"fast", "near", "span", "near+span"};
+        search = -1;
+        for (int i = 0; i < 4; ++i)
+            if (!strcmp(w, names[i])) search = i;
+        if (search < 0)
+            return oge_fail(nullptr, OGE_ERR_ARG,
+                            (std::string("oge_ctx_create: OGE_DEFLATE_SEARCH=") + w + " (fast, near, span or near+span)").c_str());
+    }
     oge_ctx *c = new oge_ctx();
     c->device = device;
+    c->deflate_search = search;
     e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
@@ -198,6 +209,16 @@ int oge_ctx_set_stream(oge_ctx *ctx, void *stream) {
     }
     return OGE_OK;
 }
+
+int oge_ctx_set_deflate_search(oge_ctx *ctx, int search) {
+    if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
+    if (search < OGE_DEFL_FAST || search > (OGE_DEFL_NEAR | OGE_DEFL_SPAN))
+        return oge_fail(ctx, OGE_ERR_ARG, "deflate search must be 0..3 (OGE_DEFL_*)");
+    ctx->deflate_search = search;
+    return OGE_OK;
+}
+
+int oge_ctx_deflate_search(oge_ctx *ctx) { return ctx ? ctx->deflate_search : (int)OGE_ERR_ARG; }
 
 void *oge_ctx_stream(oge_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
 

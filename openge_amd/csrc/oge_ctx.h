@@ -28,6 +28,7 @@ struct oge_ctx {
     size_t event_pool_used = 0;
     bool timing = true;
     int timing_hold = 0;  // > 0: a composite entry point (the pipeline) keeps its sub-calls' stage events
+    int deflate_search = OGE_DEFL_FAST;  // the GPU deflate's match search (oge_ctx_set_deflate_search)
     bool pool = false;  // allocate from the device's stream-ordered pool and keep freed memory in it
     hipStream_t side[4] = {nullptr, nullptr, nullptr, nullptr};  // extra streams a stage pipelines over
     hipStream_t side_stream(int i);

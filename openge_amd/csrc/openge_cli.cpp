@@ -38,7 +38,8 @@ const Opt kGlobal[] = {{"v", "verbose", false}, {"t", "threads", true}, {"d", "n
                        {"T", "tmpdir", true},   {"", "nosplit", false},  {"i", "in", true},
                        {"F", "format", true},   {"c", "compression", true}, {"", "nopg", false},
                        {"", "device", true},    {"", "compat-nonverbose-dedup", false},
-                       {"", "split-chains", true}, {"", "compat-split", false}, {"", "gpus", true}};
+                       {"", "split-chains", true}, {"", "compat-split", false}, {"", "gpus", true},
+                       {"", "deflate-search", true}};
 const Opt kMergesort[] = {{"o", "out", true}, {"r", "region", true},  {"q", "mapq", true},
                           {"b", "byname", false}, {"n", "n", true}, {"C", "compresstempfiles", false},
                           {"M", "markduplicates", false}, {"R", "removeduplicates", false}};
@@ -102,7 +103,12 @@ bool parse(int argc, const char **argv, const std::vector<Opt> &opts, Parsed &p)
 }
 
 void usage_top() {
-    fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, version\n");
+    fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, version\n"
+                    "\nGPU options (every command):\n"
+                    "    --device N              first GPU\n"
+                    "    --gpus G                ranks over G GPUs\n"
+                    "    --deflate-search NAME   match search of the GPU BAM writer: fast (default), near, span or\n"
+                    "                            near+span (smaller files; see oge_ctx_set_deflate_search)\n");
 }
 
 }  // namespace
@@ -153,6 +159,15 @@ int main(int argc, const char **argv) {
     if (split > 1 && compat) {
         fprintf(stderr, "openge: split chains with --compat-nonverbose-dedup are not supported\n");
         return -1;
+    }
+    if (p.count("deflate-search")) {
+        // through the environment: every context the command creates (the chain's, each rank's) reads it
+        const std::string s = p.get("deflate-search", "fast");
+        if (s != "fast" && s != "near" && s != "span" && s != "near+span") {
+            fprintf(stderr, "openge: --deflate-search %s: fast, near, span or near+span\n", s.c_str());
+            return -1;
+        }
+        setenv("OGE_DEFLATE_SEARCH", s.c_str(), 1);
     }
     timeval t0;
     gettimeofday(&t0, nullptr);

@@ -6,6 +6,7 @@ the library only runs kernels on the context's stream.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from pathlib import Path
@@ -16,6 +17,7 @@ PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["OGE_LIB"]) if os.environ.get("OGE_LIB") else PKG / "libopenge_hip.so"  # OGE_LIB: an A/B build
 
 MAX_REF = 64
+DEFLATE_SEARCH = ("fast", "near", "span", "near+span")  # OGE_DEFL_* values 0..3 (include/openge_hip.h)
 
 
 class SynthParams(C.Structure):
@@ -244,6 +246,8 @@ def lib() -> C.CDLL:
         "oge_memcpy": (C.c_int, [vp, vp, vp, u64, C.c_int]),
         "oge_host_alloc": (C.c_int, [vp, u64, C.POINTER(vp)]),
         "oge_ctx_set_pool": (C.c_int, [vp, C.c_int]),
+        "oge_ctx_set_deflate_search": (C.c_int, [vp, C.c_int]),
+        "oge_ctx_deflate_search": (C.c_int, [vp]),
         "oge_host_free": (C.c_int, [vp, vp]),
         "oge_realign_opts_init": (None, [vp]),
         "oge_localrealign": (C.c_int, [vp, C.c_char_p, u64, vp, vp, u64, C.c_char_p, C.c_char_p, vp, C.POINTER(vp)]),
@@ -492,18 +496,46 @@ class Context:
         """oge_exclusive_scan_dev: exclusive prefix sum of n u32 (elem_bytes 4) or u64 (8) device elements."""
         check(lib().oge_exclusive_scan_dev(self.h, d_in, d_out, n, elem_bytes), self.h)
 
-    def bgzf_deflate(self, data: bytes | np.ndarray, level: int = 6) -> bytes:
+    def set_deflate_search(self, search: str | int) -> None:
+        """The GPU deflate's match search for this context: "fast" (0, the default), "near" (1), "span" (2)
+        or "near+span" (3) -- see oge_ctx_set_deflate_search."""
+        if isinstance(search, str):
+            if search not in DEFLATE_SEARCH:
+                raise OgeError(f"deflate search {search!r}: one of {', '.join(DEFLATE_SEARCH)}")
+            search = DEFLATE_SEARCH.index(search)
+        check(lib().oge_ctx_set_deflate_search(self.h, int(search)), self.h)
+
+    @property
+    def deflate_search(self) -> int:
+        return lib().oge_ctx_deflate_search(self.h)
+
+    @contextlib.contextmanager
+    def _search(self, search: str | int | None):
+        """search for the duration of one call (None: the context's own)."""
+        if search is None:
+            yield
+            return
+        old = self.deflate_search
+        self.set_deflate_search(search)
+        try:
+            yield
+        finally:
+            self.set_deflate_search(old)
+
+    def bgzf_deflate(self, data: bytes | np.ndarray, level: int = 6, search: str | int | None = None) -> bytes:
         """BGZF-compress host bytes on the device (no EOF marker)."""
         a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
         cap = int(lib().oge_bgzf_bound(len(a)))
         out = np.empty(max(cap, 1), dtype=np.uint8)
         got = C.c_uint64()
-        check(lib().oge_bgzf_deflate(self.h, _ptr(a), len(a), level, _ptr(out), cap, C.byref(got)), self.h)
+        with self._search(search):
+            check(lib().oge_bgzf_deflate(self.h, _ptr(a), len(a), level, _ptr(out), cap, C.byref(got)), self.h)
         return out[:got.value].tobytes()
 
-    def bgzf_deflate_dev(self, d_src, n: int, level: int, d_dst, dst_cap: int) -> int:
+    def bgzf_deflate_dev(self, d_src, n: int, level: int, d_dst, dst_cap: int, search: str | int | None = None) -> int:
         got = C.c_uint64()
-        check(lib().oge_bgzf_deflate_dev(self.h, d_src, n, level, d_dst, dst_cap, C.byref(got)), self.h)
+        with self._search(search):
+            check(lib().oge_bgzf_deflate_dev(self.h, d_src, n, level, d_dst, dst_cap, C.byref(got)), self.h)
         return got.value
 
     def bgzf_inflate(self, z: bytes, out_cap: int | None = None) -> bytes:

@@ -7,6 +7,9 @@
 // symbols (code lengths limited to 15) + extra bits + a dynamic-header estimate + 26 bytes of BGZF framing.
 //
 //   gcc -O2 -o /tmp/defl_model tools/defl_model.c && /tmp/defl_model sample.bin R K lazy S hashbytes hashbits
+// Environment: LOC=11 adds the round-local table of the NEAR search (2^11 buckets); with S=0 beside it the
+// SPAN search's uncut matches (the kernel still cuts at 32,768: one cut per sub-block more than this model).
+// DESIGN §10's real-data table: the inflated tests/golden/inputs/208.yhet.bam with `1024 1 0 64 4 12`.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -202,6 +205,25 @@ static uint64_t payload_bits(const uint8_t *in, int n, const Cfg *c) {
             uint32_t h = (key * 2654435761u) >> (32 - hbits);
             prev[p] = gpuchain ? rhead[h] : head[h];
             head[h] = p + 1;
+        }
+    }
+    // LOC=bits: a round-local table (k_defl_parse_x's NEAR): the earliest position e of p's own round with the
+    // same bucket (the top `bits` bits of the same hash); when e < p and their 4 bytes are equal, e becomes p's
+    // first candidate (the nearest one; with K = 1 it replaces the earlier rounds' candidate)
+    const char *loce = getenv("LOC");
+    for (int r = 0; loce && c->K > 0 && r < n; r += c->R) {
+        static int32_t lfirst[1 << 16];
+        const int lb = atoi(loce), e = r + c->R < n ? r + c->R : n;
+        for (int p = e - 1; p >= r; --p)
+            if (p + 4 <= n) lfirst[(rd32(in + p) * 2654435761u) >> (32 - lb)] = p;
+        for (int p = r; p < e; ++p) {
+            if (p + 4 > n) continue;
+            const int f = lfirst[(rd32(in + p) * 2654435761u) >> (32 - lb)];
+            if (f >= p || rd32(in + f) != rd32(in + p)) continue;
+            int k = ncand[p] < c->K ? ncand[p] : c->K - 1;  // room for one more, or the farthest one goes
+            for (; k > 0; --k) cand[p][k] = cand[p][k - 1];
+            cand[p][0] = f;
+            if (ncand[p] < c->K) ncand[p]++;
         }
     }
     (void)rhead;
