@@ -166,7 +166,9 @@ typedef struct oge_mergesort_opts {
     int32_t remove_duplicates;       /* -R (with -M) */
     int32_t compat_nonverbose_index; /* oge_markdup_opts field of the same name */
     int32_t split_chains;            /* oge_markdup_opts field of the same name */
-    int32_t pad0;
+    int32_t build_index;             /* != 0: oge_mergesort_bgzf_dev also builds the .bai of the file it returns
+                                      * (fetch it with oge_ctx_last_bai).  oge_mergesort_bgzf_host / _dist / _shard
+                                      * fail with OGE_ERR_ARG ("index not provided on this path") when it is set. */
     const char *program_line;        /* @PG CL, or NULL (--nopg) */
 } oge_mergesort_opts;
 void oge_mergesort_opts_init(oge_mergesort_opts *o);
@@ -455,6 +457,34 @@ int oge_fix_bins_dev(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off, uint6
  * records): the writer side of -r/-R (MarkDuplicates::runInternal, mark_duplicates.cpp:456-458). */
 int oge_drop_flagged_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, uint16_t flag_mask,
                          uint8_t *d_out, uint64_t *d_out_off, uint64_t *n_out);
+
+/* ---- BAM index (.bai, SAM v1 section 5.2) of coordinate-sorted records, built on the device ---------
+ * The reference writes no index (util/bam_index.cpp:245-246 returns at once); the image is one canonical
+ * byte string per input: a chunk is a maximal run of consecutive records with one
+ * (refID, bin), chunks of a bin stay in file order and merge when the next starts in the compressed block
+ * its predecessor ends in (or an earlier one), bins ascend, pseudo-bin 37450 comes last, nothing is promoted
+ * to parent bins, and empty linear windows take the next window's offset.  Not byte-equal to samtools'
+ * index, and valid for every BAI reader.
+ * Records d_recs + d_off[i] (n offsets), contiguous as in the stream; record 0 sits at decompressed-stream
+ * position stream_base.  Block table: d_uoff / d_cstart hold nblk + 1 entries, payload offset and file offset
+ * of every block, entry nblk = payload total / the file offset just past the last data block.  Input must be
+ * in the project's coordinate order (refID ascending with -1 last, pos ascending): the first violation fails
+ * with OGE_ERR_ARG naming the record index; a record that ends past 2^29, or n_ref < 0, with OGE_ERR_LIMIT.
+ * *d_bai (device) is valid until the next call on ctx.  Stage name for oge_ctx_timing: "bai_build". */
+int oge_bai_build_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref,
+                      uint64_t stream_base, const uint64_t *d_uoff, const uint64_t *d_cstart, uint64_t nblk,
+                      const uint8_t **d_bai, uint64_t *bai_bytes);
+/* Host-buffer form (uploads, builds, downloads into out when cap holds it; *bai_bytes = the image size,
+ * OGE_ERR_LIMIT when cap is smaller). */
+int oge_bai_build(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const uint64_t *rec_off, uint64_t n,
+                  int32_t n_ref, uint64_t stream_base, const uint64_t *uoff, const uint64_t *cstart, uint64_t nblk,
+                  uint8_t *out, uint64_t cap, uint64_t *bai_bytes);
+/* A whole BAM file resident in HBM (4-byte aligned) -> its index: framing index, inflate, header, record
+ * walk, build.  Blocks with an empty payload are not part of the block table. */
+int oge_bam_index_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const uint8_t **d_bai, uint64_t *bai_bytes);
+/* The index the context's last oge_bai_build* / oge_bam_index_dev / oge_mergesort_bgzf_dev(build_index) call
+ * built; OGE_ERR_ARG when there is none. */
+int oge_ctx_last_bai(oge_ctx *ctx, const uint8_t **d_bai, uint64_t *bai_bytes);
 
 /* ---- mergesort extras: Filter (-r region / -q mapq) and sort by name (-b) ----------- */
 /* Filter::runInternal's predicate (algorithms/filter.cpp:205-249) with the module's setters

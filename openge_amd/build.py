@@ -22,7 +22,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXX = os.environ.get("CXX", "g++")
 ARCH = "gfx950"
 
-HIP_SRCS = ["prims.hip", "sort.hip", "records.hip", "markdup.hip", "capi_dev.hip", "realign.hip", "realign_prep.hip", "bgzf.hip", "inflate.hip", "inflate_lane.hip", "filter.hip", "sort_name.hip", "pipeline.hip", "dist.hip", "shard.hip", "chunked.hip"]
+HIP_SRCS = ["prims.hip", "sort.hip", "records.hip", "markdup.hip", "capi_dev.hip", "realign.hip", "realign_prep.hip", "bgzf.hip", "inflate.hip", "inflate_lane.hip", "filter.hip", "sort_name.hip", "pipeline.hip", "bai.hip", "dist.hip", "shard.hip", "chunked.hip"]
 HOST_SRCS = ["bamio.cpp", "host_capi.cpp", "realign.cpp", "realign_synth.cpp"]
 CLI_SRCS = ["openge_cli.cpp", "modules.cpp"]
 
@@ -59,6 +59,11 @@ def _compile(src: Path, obj: Path, hip: bool) -> None:
 
 
 def build(verbose: bool = False) -> Path:
+    # a tree that travels with its library and CLI but without the object files: nothing to do when both
+    # are newer than every source and header
+    srcs = [CSRC / s for s in HIP_SRCS + HOST_SRCS + CLI_SRCS if (CSRC / s).exists()] + _headers()
+    if not _stale(LIB, srcs) and not _stale(CLI, srcs + [LIB]):
+        return LIB
     jobs = []
     for s in HIP_SRCS:
         if (CSRC / s).exists():

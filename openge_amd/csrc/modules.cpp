@@ -1224,6 +1224,10 @@ int FileWriter::write_device(ChainContext &cc, ReadBatch &b, BgzfWriter &w, doub
     }
     if (getenv("OGE_WRITE_TRACE")) fprintf(stderr, "[openge] FileWriter: buffers %.3f s\n", sec(t, clk()));
     w.write_compressed(nullptr, 0);  // flush the header as blocks of its own
+    // --index: the block table of the file, from the BSIZE fields of the bytes that go to it (the header's
+    // blocks hold no record: the table starts behind them)
+    std::vector<uint64_t> ix_uoff, ix_cstart;
+    uint64_t ix_u = index_hdr_u_, ix_z = index_hdr_z_;
     int k = 0;
     for (uint64_t s0 = 0; s0 < len; s0 += seg, k ^= 1) {
         const uint64_t sl = std::min(seg, len - s0);
@@ -1245,11 +1249,48 @@ int FileWriter::write_device(ChainContext &cc, ReadBatch &b, BgzfWriter &w, doub
         }
         *t_d2h += sec(t, clk());
         const uint8_t *hp = (const uint8_t *)hz[k];
+        if (index_) {
+            uint64_t nb = 0;
+            const int rc = oge_bgzf_index(hp, zb, nullptr, nullptr, nullptr, nullptr, 0, &nb);
+            std::vector<uint64_t> d0(nb + 1), uo(nb + 1);
+            if ((rc != OGE_OK && rc != OGE_ERR_ARG) || oge_bgzf_index(hp, zb, d0.data(), nullptr, uo.data(), nullptr, nb, &nb)) {
+                release();
+                return cc.fail("FileWriter: index of the written blocks");
+            }
+            for (uint64_t i = 0; i < nb; ++i) {  // the device writer's blocks have 18-byte headers
+                ix_cstart.push_back(ix_z + d0[i] - 18);
+                ix_uoff.push_back(ix_u + uo[i]);
+            }
+            ix_u += uo[nb];
+            ix_z += zb;
+        }
         wr = std::thread([&w, hp, zb]() { w.write_compressed(hp, zb); });
     }
     t = clk();
     if (wr.joinable()) wr.join();
     *t_wait += sec(t, clk());
+    if (index_) {  // before release() frees the kept records
+        ix_uoff.push_back(ix_u);
+        ix_cstart.push_back(ix_z);
+        const uint64_t nblk = ix_uoff.size() - 1;
+        void *tab = nullptr;
+        const uint8_t *d_bai = nullptr;
+        uint64_t bb = 0;
+        int rc = oge_dev_alloc(cc.ctx, 2 * (nblk + 1) * 8, &tab);
+        uint64_t *dt = (uint64_t *)tab;
+        if (!rc) rc = oge_memcpy(cc.ctx, dt, ix_uoff.data(), (nblk + 1) * 8, 1);
+        if (!rc) rc = oge_memcpy(cc.ctx, dt + nblk + 1, ix_cstart.data(), (nblk + 1) * 8, 1);
+        if (!rc) rc = oge_bai_build_dev(cc.ctx, recs, offs, n, (int32_t)b.header.sq.size(), index_hdr_u_, dt, dt + nblk + 1, nblk, &d_bai, &bb);
+        if (!rc) {
+            bai_.resize(bb);
+            rc = oge_memcpy(cc.ctx, bai_.data(), d_bai, bb, 2);
+        }
+        if (tab) oge_dev_free(cc.ctx, tab);
+        if (rc) {
+            release();
+            return cc.fail("FileWriter: index");
+        }
+    }
     t = clk();
     release();
     if (getenv("OGE_WRITE_TRACE")) fprintf(stderr, "[openge] FileWriter: release %.3f s\n", sec(t, clk()));
@@ -1397,6 +1438,18 @@ int FileWriter::runInternal(ChainContext &cc, ReadBatch &b) {
             b.host_valid = false;  // write_device reads the device copy
         }
     }
+    if (index_) {  // refused before anything is written
+        const char *why = filename_ == "stdout" || filename_ == "-" ? "output to stdout"
+                          : sliced                                   ? "--gpus"
+                          : produced                                 ? "output larger than device memory (chunked sort)"
+                          : !on_device                               ? "the host writer"
+                          : b.header.sort_order == BamHeaderModel::QUERYNAME ? "output sorted by name"
+                                                                     : nullptr;
+        if (why) {
+            fprintf(stderr, "openge: --index is not provided with %s\n", why);
+            return -1;
+        }
+    }
     if (!on_device && cc.to_host(b)) return -1;
     const auto t1 = clk();
     if (!on_device) fix_bins(b, cc.threads);
@@ -1413,6 +1466,12 @@ int FileWriter::runInternal(ChainContext &cc, ReadBatch &b) {
         BgzfWriter w(f, level_, cc.threads > 0 ? cc.threads : 8);
         std::vector<uint8_t> hb = bam_encode_header(h);
         w.write(hb.data(), hb.size());
+        if (index_) {  // the header's blocks are flushed now (write_device would do it next): their size in the file
+            w.write_compressed(nullptr, 0);
+            fflush(f);
+            index_hdr_z_ = (uint64_t)ftello(f);
+            index_hdr_u_ = hb.size();
+        }
         if (on_device) {
             if (produced ? write_ranges(cc, b, w) : sliced ? write_slices(cc, b, w) : write_device(cc, b, w, &t_dev, &t_d2h, &t_wait)) {
                 w.abandon();  // no EOF block and no write into the FILE closed below
@@ -1448,6 +1507,16 @@ int FileWriter::runInternal(ChainContext &cc, ReadBatch &b) {
         fprintf(stderr, "openge: error writing %s: %s\n", filename_.c_str(), strerror(errno));
         return -1;
     }
+    if (index_) {  // only beside a BAM that was written whole
+        const std::string ip = filename_ + ".bai";
+        FILE *fi = fopen(ip.c_str(), "wb");
+        const bool ok = fi && fwrite(bai_.data(), 1, bai_.size(), fi) == bai_.size();
+        if ((fi && fclose(fi) != 0) || !ok) {
+            fprintf(stderr, "openge: error writing %s: %s\n", ip.c_str(), strerror(errno));
+            remove(ip.c_str());
+            return -1;
+        }
+    }
     if (verbose_ && on_device)
         fprintf(stderr, "[openge] FileWriter: device bins + BGZF %.3f s (gpu, segmented), device->host %.3f s, waiting on the disk %.3f s, "
                 "total %.3f s\n", t_dev, t_d2h, t_wait, sec(t2, clk()));
@@ -1455,6 +1524,36 @@ int FileWriter::runInternal(ChainContext &cc, ReadBatch &b) {
         fprintf(stderr, "[openge] FileWriter: device->host %.3f s, bins %.3f s, BGZF %.3f s (%s)\n", sec(t0, t1), sec(t1, t2),
                 sec(t2, clk()), bgzf_codec_name());
     else fflush(stdout);
+    return 0;
+}
+
+int index_bam_file(ChainContext &cc, const std::string &path, const std::string &out) {
+    bytevec z;
+    std::string err;
+    if (!read_file_bytes(path, z, cc.threads > 0 ? cc.threads : 8, err)) {
+        fprintf(stderr, "openge: %s: %s\n", path.c_str(), err.c_str());
+        return -1;
+    }
+    void *dz = nullptr;
+    const uint8_t *d_bai = nullptr;
+    uint64_t bb = 0;
+    std::vector<uint8_t> img;
+    int rc = oge_dev_alloc(cc.ctx, z.size() + 64, &dz);
+    if (!rc) rc = oge_memcpy(cc.ctx, dz, z.data(), z.size(), 1);
+    if (!rc) rc = oge_bam_index_dev(cc.ctx, (const uint8_t *)dz, z.size(), &d_bai, &bb);
+    if (!rc) {
+        img.resize(bb);
+        rc = oge_memcpy(cc.ctx, img.data(), d_bai, bb, 2);
+    }
+    if (dz) oge_dev_free(cc.ctx, dz);
+    if (rc) return cc.fail("index");
+    FILE *f = fopen(out.c_str(), "wb");
+    const bool ok = f && fwrite(img.data(), 1, img.size(), f) == img.size();
+    if ((f && fclose(f) != 0) || !ok) {
+        fprintf(stderr, "openge: error writing %s: %s\n", out.c_str(), strerror(errno));
+        remove(out.c_str());
+        return -1;
+    }
     return 0;
 }
 

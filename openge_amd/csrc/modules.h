@@ -207,10 +207,19 @@ public:
     int write_ranges(ChainContext &cc, ReadBatch &b, BgzfWriter &w);
     void addProgramLine(const std::string &cl) { program_line_ = cl; }
     int setFormat(const std::string &f);  // only "bam" is supported (SAM/FASTQ out of scope)
+    // --index: <out>.bai beside the BAM, built on the device from the records write_device compresses
+    // (oge_bai_build_dev); only the one-GPU device writer provides it, every other path fails before it writes
+    void setIndex(bool on) { index_ = on; }
 protected:
     int runInternal(ChainContext &cc, ReadBatch &b) override;
     std::string filename_ = "stdout", program_line_;
     int level_ = 6;
+    bool index_ = false;
+    uint64_t index_hdr_z_ = 0, index_hdr_u_ = 0;  // compressed / decompressed size of the header blocks
+    std::vector<uint8_t> bai_;                    // the index image write_device built
 };
+
+// `openge index in.bam [-o out.bai]`: the file into HBM, oge_bam_index_dev, the image to out (in.bam.bai)
+int index_bam_file(ChainContext &cc, const std::string &path, const std::string &out);
 
 }  // namespace oge

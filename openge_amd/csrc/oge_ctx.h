@@ -57,6 +57,8 @@ struct oge_ctx {
     // the inflate's phase-1 bitmap buffer and how many of its bytes are known clear (inflate_lane.hip)
     const void *infl_clean_ptr = nullptr;
     uint64_t infl_clean_bytes = 0, infl_clean_next = 0;
+    const uint8_t *bai_ptr = nullptr;  // the index image of the last call that built one (workspace "bai_image")
+    uint64_t bai_bytes = 0;
     std::map<std::string, uint64_t> counters;  // per call: work counts a stage reports (oge_ctx_counter)
     bool last_scan_generic = false;  // realign scan fell back to the byte-wise kernel
     double scan_t[3] = {0, 0, 0};    // realign scan host timings: validate, upload, device + download
@@ -149,6 +151,14 @@ bool oge_bgzf_index_host_mt(const uint8_t *z, uint64_t zbytes, int T, std::vecto
 int oge_inflate_lanes(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const uint64_t *d0, const uint64_t *d1,
                       const uint64_t *uoff, const uint32_t *crc, uint64_t nblk, uint8_t *out, uint32_t *err,
                       const uint32_t *zpow);
+
+// ---- BAM index (bai.hip) ----
+// oge_bai_build_dev without the argument checks and the timing reset (the chain calls it under its own hold)
+int oge_bai_build_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref, uint64_t stream_base,
+                       const uint64_t *d_uoff, const uint64_t *d_cstart, uint64_t nblk, const uint8_t **d_bai, uint64_t *bai_bytes);
+// file offsets of the indexed blocks of d_z (nblk + 1 entries, workspace "bai_cstart"): cstart[nblk] = the end
+// of the last one; the oge_bai_build_impl call that consumes the table releases it
+int oge_bai_cstart(oge_ctx *ctx, const uint8_t *d_z, const uint64_t *d0, const uint64_t *d1, uint64_t nblk, uint64_t **cstart_out);
 
 // ---- multi-GPU internals (dist.hip)
 oge_ctx *oge_comm_ctx(oge_comm *comm);

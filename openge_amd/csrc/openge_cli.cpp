@@ -42,8 +42,9 @@ const Opt kGlobal[] = {{"v", "verbose", false}, {"t", "threads", true}, {"d", "n
                        {"", "deflate-search", true}};
 const Opt kMergesort[] = {{"o", "out", true}, {"r", "region", true},  {"q", "mapq", true},
                           {"b", "byname", false}, {"n", "n", true}, {"C", "compresstempfiles", false},
-                          {"M", "markduplicates", false}, {"R", "removeduplicates", false}};
-const Opt kDedup[] = {{"o", "out", true}, {"r", "remove", false}};
+                          {"M", "markduplicates", false}, {"R", "removeduplicates", false}, {"", "index", false}};
+const Opt kDedup[] = {{"o", "out", true}, {"r", "remove", false}, {"", "index", false}};
+const Opt kIndex[] = {{"o", "out", true}};
 const Opt kRealign[] = {{"o", "out", true}, {"R", "reference", true}, {"L", "intervals", true}};
 
 struct Parsed {
@@ -103,7 +104,9 @@ bool parse(int argc, const char **argv, const std::vector<Opt> &opts, Parsed &p)
 }
 
 void usage_top() {
-    fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, version\n"
+    fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, index, version\n"
+                    "\n    openge index in.bam [-o out.bai]    BAM index of a coordinate-sorted file (default in.bam.bai)\n"
+                    "    mergesort / sort / dedup --index    also write <out>.bai (one GPU, file output, coordinate order)\n"
                     "\nGPU options (every command):\n"
                     "    --device N              first GPU\n"
                     "    --gpus G                ranks over G GPUs\n"
@@ -132,6 +135,7 @@ int main(int argc, const char **argv) {
     if (cmd == "mergesort") opts.insert(opts.end(), std::begin(kMergesort), std::end(kMergesort));
     else if (cmd == "dedup") opts.insert(opts.end(), std::begin(kDedup), std::end(kDedup));
     else if (cmd == "localrealign") opts.insert(opts.end(), std::begin(kRealign), std::end(kRealign));
+    else if (cmd == "index") opts.insert(opts.end(), std::begin(kIndex), std::end(kIndex));
     else {
         fprintf(stderr, "Unknown command %s.\n", argv[1]);
         return -1;
@@ -169,6 +173,20 @@ int main(int argc, const char **argv) {
         }
         setenv("OGE_DEFLATE_SEARCH", s.c_str(), 1);
     }
+    if (p.count("index")) {  // what the index is not provided with fails before anything is read or written
+        const char *why = p.get("out", "stdout") == "stdout" || p.get("out", "stdout") == "-" ? "output to stdout"
+                          : cc.gpus > 1                                                        ? "--gpus"
+                          : p.count("byname")                                                  ? "-b (sort by name)"
+                                                                                               : nullptr;
+        if (why) {
+            fprintf(stderr, "openge: --index is not provided with %s\n", why);
+            return -1;
+        }
+    }
+    if (cmd == "index" && (p.inputs.size() != 1 || p.inputs[0] == "stdin" || p.inputs[0] == "-")) {
+        fprintf(stderr, "openge index: one BAM file is required\n");
+        return -1;
+    }
     timeval t0;
     gettimeofday(&t0, nullptr);
     // one input file on one GPU: its bytes come off the disk / page cache while HIP initialises
@@ -182,11 +200,17 @@ int main(int argc, const char **argv) {
         fprintf(stderr, "openge: %s\n", oge_last_error(cc.ctx));
         return -1;
     }
+    if (cmd == "index") {
+        const int r = index_bam_file(cc, p.inputs[0], p.get("out", p.inputs[0] + ".bai"));
+        oge_ctx_destroy(cc.ctx);
+        return r;
+    }
 
     FileReader reader;
     FileWriter writer;
     reader.addFiles(p.inputs);
     writer.setFilename(p.get("out", "stdout"));
+    writer.setIndex(p.count("index"));
     if (!p.count("nopg")) writer.addProgramLine(command_line);
     writer.setCompressionLevel(level);
     if (p.count("format") && writer.setFormat(p.get("format", "bam"))) return -1;

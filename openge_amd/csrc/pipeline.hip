@@ -15,6 +15,7 @@
 //   sort     oge_sort_markdup_dev (or sort + gather without -M) X -> Y, bins recomputed
 //   [-R]     oge_drop_flagged_dev Y -> X
 //   write    header block (host) + oge_bgzf_deflate_dev + EOF block into the free buffer
+//   [index]  build_index: framing walk of the written file, oge_bai_build_impl on the records (bai.hip)
 //
 // oge_mergesort_bgzf_dist runs the same chain over G ranks (one input file per rank, the sort and
 // dedup through oge_sort_markdup_dist, every rank deflating its own output slice);
@@ -84,12 +85,11 @@ extern "C" void oge_mergesort_opts_init(oge_mergesort_opts *o) {
     o->level = 6;  // FileWriter's default compression level (commands.cpp:129, -c)
 }
 
-static int decode_records(oge_ctx *ctx, uint8_t *X, uint64_t total, uint64_t **xoff_o, uint64_t *n_o, BamFile *f);
+static int decode_records(oge_ctx *ctx, uint8_t *X, uint64_t total, uint64_t **xoff_o, uint64_t *n_o, BamFile *f,
+                          uint64_t *rec_base_o = nullptr);
 
-// The reader half: framing index, inflate into X (ws "pipe_x", *cap bytes), header parse, record walk.
-static int decode(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint8_t **Xo, uint64_t *cap_out, uint64_t **xoff_o,
-                  uint64_t *n_o, BamFile *f) {
-    // ---- framing index (device; host walk of a copy when the chain is not exact)
+// The framing index of a BGZF file in HBM (device walk; host walk of a copy when the chain is not exact).
+static int index_file(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, OgeBgzfIndex *ixo) {
     OgeStageTimer *tm = ctx->begin_stage("bgzf_index");
     OgeBgzfIndex ix;
     int rc = oge_bgzf_index_ws(ctx, d_z, zbytes, &ix);
@@ -108,6 +108,17 @@ static int decode(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint8_t **X
         OGE_HIP_TRY(ctx, hipMemcpyAsync(&ix.total, ix.uoff + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
         OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
+    *ixo = ix;
+    return OGE_OK;
+}
+
+// The reader half: framing index, inflate into X (ws "pipe_x", *cap bytes), header parse, record walk.
+static int decode(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint8_t **Xo, uint64_t *cap_out, uint64_t **xoff_o,
+                  uint64_t *n_o, BamFile *f, OgeBgzfIndex *ixo = nullptr, uint64_t *rec_base_o = nullptr) {
+    OgeBgzfIndex ix;
+    int rc = index_file(ctx, d_z, zbytes, &ix);
+    if (rc) return rc;
+    if (ixo) *ixo = ix;
     const uint64_t total = ix.total;
     if (!total) return oge_fail(ctx, OGE_ERR_IO, "empty BAM stream (no BAM magic)");
 
@@ -120,12 +131,12 @@ static int decode(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint8_t **X
 
     *Xo = X;
     *cap_out = cap;
-    return decode_records(ctx, X, total, xoff_o, n_o, f);
+    return decode_records(ctx, X, total, xoff_o, n_o, f, rec_base_o);
 }
 
 // The reader's second half on the decompressed stream X[0, total): header parse (host, a copy of the
 // first bytes), record walk.
-static int decode_records(oge_ctx *ctx, uint8_t *X, uint64_t total, uint64_t **xoff_o, uint64_t *n_o, BamFile *f) {
+static int decode_records(oge_ctx *ctx, uint8_t *X, uint64_t total, uint64_t **xoff_o, uint64_t *n_o, BamFile *f, uint64_t *rec_base_o) {
     int rc = OGE_OK;
     OgeStageTimer *tm = nullptr;
     // ---- header (host parse of the stream's first bytes)
@@ -158,6 +169,7 @@ static int decode_records(oge_ctx *ctx, uint8_t *X, uint64_t total, uint64_t **x
     ctx->end_stage(tm);
     *xoff_o = xoff;
     *n_o = n;
+    if (rec_base_o) *rec_base_o = rec_base;
     return OGE_OK;
 }
 
@@ -249,6 +261,8 @@ extern "C" int oge_mergesort_bgzf_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t
     Hold hold(ctx);
     *d_out = nullptr;
     *out_bytes = 0;
+    ctx->bai_ptr = nullptr;  // oge_ctx_last_bai: this call's index or none
+    ctx->bai_bytes = 0;
     uint8_t *X;
     uint64_t cap, *xoff, n;
     BamFile f;
@@ -264,11 +278,45 @@ extern "C" int oge_mergesort_bgzf_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t
     uint64_t ob = 0;
     rc = encode(ctx, src, soff, m, &hb, true, mo->level, dst, cap, &ob);
     if (rc) return rc;
+    if (mo->build_index) {
+        // the block table of the file just written (header blocks included), then the index of the records
+        // it holds: they sit at src + soff[i] (with -R in the other arena), the first at stream position
+        // hb.size()
+        OgeBgzfIndex ox;
+        rc = index_file(ctx, dst, ob, &ox);
+        uint64_t *cstart = nullptr;
+        if (!rc) rc = oge_bai_cstart(ctx, dst, ox.d0, ox.d1, ox.nblk, &cstart);
+        if (!rc)
+            rc = oge_bai_build_impl(ctx, src, soff, m, (int32_t)f.ref_names.size(), hb.size(), ox.uoff, cstart, ox.nblk, nullptr, nullptr);
+        if (rc) return rc;
+    }
     *d_out = dst;
     *out_bytes = ob;
     if (n_reads) *n_reads = m;
     if (n_dup) *n_dup = nd;
     return OGE_OK;
+}
+
+// A whole BAM file resident in HBM -> its index: the reader half of the chain, then the index of the records
+// where they lie in the decompressed stream.
+extern "C" int oge_bam_index_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const uint8_t **d_bai, uint64_t *bai_bytes) {
+    if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
+    if (!d_bai || !bai_bytes || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
+    (void)hipSetDevice(ctx->device);
+    Hold hold(ctx);
+    *d_bai = nullptr;
+    *bai_bytes = 0;
+    ctx->bai_ptr = nullptr;
+    ctx->bai_bytes = 0;
+    uint8_t *X;
+    uint64_t cap, *xoff, n, rec_base = 0, *cstart = nullptr;
+    BamFile f;
+    OgeBgzfIndex ix;
+    int rc = decode(ctx, d_z, zbytes, &X, &cap, &xoff, &n, &f, &ix, &rec_base);
+    if (!rc) rc = oge_bai_cstart(ctx, d_z, ix.d0, ix.d1, ix.nblk, &cstart);
+    if (rc) return rc;
+    // xoff are absolute stream positions: record 0 sits at xoff[0] (= rec_base when there are records)
+    return oge_bai_build_impl(ctx, X, xoff, n, (int32_t)f.ref_names.size(), rec_base, ix.uoff, cstart, ix.nblk, d_bai, bai_bytes);
 }
 
 // The same chain on a BAM file in HOST memory with the PCIe transfers overlapped (the
@@ -288,6 +336,7 @@ extern "C" int oge_mergesort_bgzf_host(oge_ctx *ctx, const uint8_t *h_z, uint64_
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!mo || !out_bytes || !h_out || (zbytes && !h_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
     if (mo->level < 0 || mo->level > 9) return oge_fail(ctx, OGE_ERR_ARG, "level must be 0..9");
+    if (mo->build_index) return oge_fail(ctx, OGE_ERR_ARG, "index not provided on this path");
     (void)hipSetDevice(ctx->device);
     Hold hold(ctx);
     *out_bytes = 0;
@@ -530,6 +579,7 @@ static int dist_args(oge_comm *comm, const uint8_t *d_z, uint64_t zbytes, const 
     oge_ctx *ctx = oge_comm_ctx(comm);
     if (!mo || !d_out || !out_bytes || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
     if (mo->level < 0 || mo->level > 9) return oge_fail(ctx, OGE_ERR_ARG, "level must be 0..9");
+    if (mo->build_index) return oge_fail(ctx, OGE_ERR_ARG, "index not provided on this path");
     (void)hipSetDevice(ctx->device);
     *d_out = nullptr;
     *out_bytes = 0;

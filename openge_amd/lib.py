@@ -54,7 +54,7 @@ class MergesortOpts(C.Structure):
     """Mirror of oge_mergesort_opts (include/openge_hip.h)."""
 
     _fields_ = [(k, C.c_int32) for k in ("level", "mark_duplicates", "remove_duplicates", "compat_nonverbose_index",
-                                         "split_chains", "pad0")] + [("program_line", C.c_char_p)]
+                                         "split_chains", "build_index")] + [("program_line", C.c_char_p)]
 
 
 def mergesort_opts(**over) -> MergesortOpts:
@@ -275,6 +275,10 @@ def lib() -> C.CDLL:
         "oge_sort_name_dev": (C.c_int, [vp, vp, vp, u64, vp]),
         "oge_sort_name": (C.c_int, [vp, vp, u64, vp, u64, vp]),
         "oge_bgzf_index_dev": (C.c_int, [vp, vp, u64, vp, vp, vp, vp, u64, C.POINTER(u64)]),
+        "oge_bai_build_dev": (C.c_int, [vp, vp, vp, u64, i32, u64, vp, vp, u64, C.POINTER(vp), C.POINTER(u64)]),
+        "oge_bai_build": (C.c_int, [vp, vp, u64, vp, u64, i32, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]),
+        "oge_bam_index_dev": (C.c_int, [vp, vp, u64, C.POINTER(vp), C.POINTER(u64)]),
+        "oge_ctx_last_bai": (C.c_int, [vp, C.POINTER(vp), C.POINTER(u64)]),
         "oge_mergesort_opts_init": (None, [vp]),
         "oge_mergesort_bgzf_dev": (C.c_int, [vp, vp, u64, vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64),
                                              C.POINTER(u64)]),
@@ -565,6 +569,58 @@ class Context:
         check(lib().oge_mergesort_bgzf_dev(self.h, d_z, zbytes, C.byref(opts), C.byref(d), C.byref(ob), C.byref(nr),
                                            C.byref(nd)), self.h)
         return d.value or 0, ob.value, nr.value, nd.value
+
+    def _fetch(self, d: int, nbytes: int) -> bytes:
+        out = np.empty(max(nbytes, 1), dtype=np.uint8)
+        check(lib().oge_memcpy(self.h, _ptr(out), d, nbytes, 2), self.h)
+        return out[:nbytes].tobytes()
+
+    def bai_build_dev(self, d_recs, d_off, n: int, n_ref: int, stream_base: int, d_uoff, d_cstart, nblk: int) -> bytes:
+        """oge_bai_build_dev: the .bai image of coordinate-sorted device records (d_off: n offsets; block table
+        d_uoff / d_cstart: nblk + 1 entries each), copied to the host."""
+        d, nb = C.c_void_p(), C.c_uint64()
+        check(lib().oge_bai_build_dev(self.h, d_recs, d_off, n, n_ref, stream_base, d_uoff, d_cstart, nblk, C.byref(d),
+                                      C.byref(nb)), self.h)
+        return self._fetch(d.value, nb.value)
+
+    def bai_build(self, recs: np.ndarray, offs: np.ndarray, n: int, n_ref: int, stream_base: int, uoff: np.ndarray,
+                  cstart: np.ndarray) -> bytes:
+        """oge_bai_build: the same from host buffers."""
+        uoff = np.ascontiguousarray(uoff, dtype=np.uint64)
+        cstart = np.ascontiguousarray(cstart, dtype=np.uint64)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nb = C.c_uint64()
+        args = (self.h, _ptr(recs), recs.nbytes, _ptr(offs), n, n_ref, stream_base, _ptr(uoff), _ptr(cstart), len(uoff) - 1)
+        rc = lib().oge_bai_build(*args, None, 0, C.byref(nb))
+        if rc != -3 or not nb.value:  # OGE_ERR_LIMIT with the size: the sizing call
+            check(rc, self.h)
+        out = np.empty(nb.value, dtype=np.uint8)
+        check(lib().oge_bai_build(*args, _ptr(out), out.nbytes, C.byref(nb)), self.h)
+        return out[:nb.value].tobytes()
+
+    def bam_index(self, bam_bytes: bytes) -> bytes:
+        """The .bai image of a whole BAM file (oge_bam_index_dev on a copy of the file in HBM)."""
+        a = np.frombuffer(bam_bytes, dtype=np.uint8)
+        dz = C.c_void_p()
+        check(lib().oge_dev_alloc(self.h, len(a) + 64, C.byref(dz)), self.h)
+        try:
+            check(lib().oge_memcpy(self.h, dz, _ptr(a), len(a), 1), self.h)
+            d, nb = C.c_void_p(), C.c_uint64()
+            check(lib().oge_bam_index_dev(self.h, dz, len(a), C.byref(d), C.byref(nb)), self.h)
+            return self._fetch(d.value, nb.value)
+        finally:
+            lib().oge_dev_free(self.h, dz)
+
+    def last_bai(self) -> bytes:
+        """The index the context's last call built (oge_ctx_last_bai); OgeError when there is none."""
+        d, nb = C.c_void_p(), C.c_uint64()
+        check(lib().oge_ctx_last_bai(self.h, C.byref(d), C.byref(nb)), self.h)
+        return self._fetch(d.value, nb.value)
+
+    def mem_info(self) -> tuple[int, int]:
+        f, t = C.c_uint64(), C.c_uint64()
+        check(lib().oge_mem_info(self.h, C.byref(f), C.byref(t)), self.h)
+        return f.value, t.value
 
     def mergesort_reserve(self, total: int) -> tuple[int, int, int]:
         """Allocate the chain's two record arenas for streams of up to `total` decompressed bytes ->
