@@ -486,6 +486,74 @@ int oge_bam_index_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const u
  * built; OGE_ERR_ARG when there is none. */
 int oge_ctx_last_bai(oge_ctx *ctx, const uint8_t **d_bai, uint64_t *bai_bytes);
 
+/* ---- stats, count and coverage of records in HBM (openge stats / count / coverage) ------------------
+ * The reference's Statistics and MeasureCoverage modules (algorithms/statistics.cpp,
+ * algorithms/measure_coverage.cpp) as reductions on the device; DESIGN.md section 20.  len = l_seq.
+ * Counters: mapped = !(flag & 4); forward / reverse by flag & 0x10; failed_qc 0x200; duplicates 0x400;
+ * paired = flag & 1; and only among paired reads proper_pair (flag & 2), read1 (0x40), read2 (0x80),
+ * both_mapped (mapped and !(flag & 8)) and singletons (mapped and flag & 8).
+ * sorted: only records with refID != -1 and pos != -1 are considered, last_rid = last_pos = -1 at the start;
+ * a lower refID than last_rid means unsorted; a higher one sets last_rid and resets last_pos to -1 WITHOUT
+ * recording this record's position; an equal one with pos < last_pos means unsorted, else last_pos = pos.
+ * So the first considered record of every refID run is exempt as a predecessor: positions 100, 50, 60 on
+ * one contig are "sorted", 100, 150, 60 are not.
+ * Inserts: over records that are paired, first mate and have tlen != 0, n_insert = their number and
+ * insert_sum = the sum of |tlen| (always filled; |INT32_MIN| counts as 2^31); with OGE_STATS_INSERTS
+ * insert_mid_lo / insert_mid_hi are the order statistics of |tlen| at ranks (n_insert - 1) / 2 and
+ * n_insert / 2 (the median is their mean), both 0 when n_insert is 0.
+ * Lengths: with OGE_STATS_LENGTHS, n_lengths and the distinct l_seq values (taken as unsigned) in
+ * ascending order with their counts. */
+typedef struct oge_bam_stats {
+    uint64_t reads, mapped, forward, reverse, failed_qc, duplicates, paired, proper_pair, read1, read2, both_mapped,
+        singletons;
+    int32_t sorted; /* 1 / 0 */
+    int32_t pad0;
+    uint64_t n_insert, insert_sum, insert_mid_lo, insert_mid_hi;
+    uint64_t n_lengths;
+} oge_bam_stats;
+enum { OGE_STATS_INSERTS = 1, OGE_STATS_LENGTHS = 2 };
+/* Records d_recs + d_off[i] (n offsets; the arena carries 16 bytes of slack behind the last record).
+ * *d_len / *d_len_count (device, n_lengths entries, only with OGE_STATS_LENGTHS; may be NULL otherwise) are
+ * valid until the next call on ctx.  Stage name for oge_ctx_timing: "qc_stats". */
+int oge_stats_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, uint32_t want,
+                  oge_bam_stats *stats, const uint32_t **d_len, const uint64_t **d_len_count);
+/* Host-buffer form: uploads, reduces, copies the length pairs into len_out / len_count_out (cap entries each;
+ * OGE_ERR_LIMIT with *stats filled when n_lengths > cap, so a first call with cap 0 sizes the arrays). */
+int oge_stats(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const uint64_t *rec_off, uint64_t n, uint32_t want,
+              oge_bam_stats *stats, uint32_t *len_out, uint64_t *len_count_out, uint64_t cap);
+/* Coverage: contig r has ceil(ref_len[r] / binsize) u32 bins, contiguous in header order:
+ * base[r] = the bins of the contigs before it, base[n_ref] = all (base has n_ref + 1 entries).
+ * OGE_ERR_ARG when binsize < 1 or n_ref < 0. */
+int oge_coverage_layout(int32_t n_ref, const int32_t *ref_len, int32_t binsize, uint64_t *base);
+/* Every record with refID != -1 and pos != -1 is counted, FLAG 0x4 reads placed at their mate included; the
+ * others add to *n_skipped.  For each of the l_seq + 1 positions i = pos .. pos + l_seq (the query length,
+ * not the CIGAR span) bin i / binsize of the contig gains 1.  A position below 0 or in a bin past the
+ * contig's last one is dropped (the reference writes outside its vector there).  *overflow = 1 when a bin
+ * reached 2^32 - 1; its value is then unspecified.  ref_len is a host array.  OGE_ERR_ARG: binsize < 1, a
+ * refID outside [-1, n_ref); OGE_ERR_LIMIT (the message names --binsize): the bins do not fit in free device
+ * memory.  *d_bins (device, base[n_ref] entries) is valid until the next call on ctx.  Stage name for
+ * oge_ctx_timing: "qc_coverage". */
+int oge_coverage_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref,
+                     const int32_t *ref_len, int32_t binsize, const uint32_t **d_bins, uint64_t *n_skipped,
+                     int32_t *overflow);
+/* Host-buffer form; bins_out holds cap entries (OGE_ERR_LIMIT when the layout needs more). */
+int oge_coverage(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const uint64_t *rec_off, uint64_t n,
+                 int32_t n_ref, const int32_t *ref_len, int32_t binsize, uint32_t *bins_out, uint64_t cap,
+                 uint64_t *n_skipped, int32_t *overflow);
+/* A whole BAM file resident in HBM (4-byte aligned): framing index, inflate, header, record walk, then the
+ * reduction.  oge_bam_coverage_dev also fails with OGE_ERR_ARG when two contigs share a name; *n_bins =
+ * base[n_ref].  oge_bam_count_dev: the number of records. */
+int oge_bam_stats_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint32_t want, oge_bam_stats *stats,
+                      const uint32_t **d_len, const uint64_t **d_len_count);
+int oge_bam_coverage_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, int32_t binsize, const uint32_t **d_bins,
+                         uint64_t *n_bins, uint64_t *n_skipped, int32_t *overflow);
+int oge_bam_count_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint64_t *n_reads);
+/* The binary reference list (names and lengths, header order) of the file the context's last oge_bam_stats_dev /
+ * oge_bam_coverage_dev / oge_bam_count_dev call parsed: *names holds the n_ref names one after the other, each
+ * NUL-terminated, *names_bytes bytes in all.  Host pointers, valid until the next such call; OGE_ERR_ARG when
+ * there is none. */
+int oge_ctx_last_refs(oge_ctx *ctx, int32_t *n_ref, const char **names, uint64_t *names_bytes, const int32_t **ref_len);
+
 /* ---- mergesort extras: Filter (-r region / -q mapq) and sort by name (-b) ----------- */
 /* Filter::runInternal's predicate (algorithms/filter.cpp:205-249) with the module's setters
  * (filter.h:34-47).  len = l_seq (BamAlignment::getLength).  A record is kept when

@@ -1557,4 +1557,235 @@ int index_bam_file(ChainContext &cc, const std::string &path, const std::string 
     return 0;
 }
 
+// ---- stats / count / coverage ------------------------------------------------------------------------
+namespace {
+
+std::chrono::steady_clock::time_point clk() { return std::chrono::steady_clock::now(); }
+double sec(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point z) {
+    return std::chrono::duration<double>(z - a).count();
+}
+
+// the file's bytes in HBM (64 bytes of slack); the caller frees *dz
+int upload_bam(ChainContext &cc, const std::string &path, void **dz, uint64_t *zbytes) {
+    bytevec z;
+    std::string err;
+    const auto t0 = clk();
+    if (!read_file_bytes(path, z, cc.threads > 0 ? cc.threads : 8, err)) {
+        fprintf(stderr, "openge: %s: %s\n", path.c_str(), err.c_str());
+        return -1;
+    }
+    const auto t1 = clk();
+    int rc = oge_dev_alloc(cc.ctx, z.size() + 64, dz);
+    if (!rc) rc = oge_memcpy(cc.ctx, *dz, z.data(), z.size(), 1);
+    if (rc) return cc.fail("upload");
+    *zbytes = z.size();
+    if (cc.verbose) fprintf(stderr, "[openge] read %.3f s, upload %.3f s\n", sec(t0, t1), sec(t1, clk()));
+    return 0;
+}
+
+void report_stages(ChainContext &cc, const char *reduce, double t_format) {
+    if (!cc.verbose) return;
+    double ix = 0, inf = 0, walk = 0, red = 0;
+    oge_ctx_timing(cc.ctx, "bgzf_index", &ix);
+    oge_ctx_timing(cc.ctx, "bgzf_inflate", &inf);
+    oge_ctx_timing(cc.ctx, "rec_walk", &walk);
+    oge_ctx_timing(cc.ctx, reduce, &red);
+    fprintf(stderr, "[openge] device: framing %.1f ms, inflate %.1f ms, record walk %.1f ms, %s %.1f ms; format %.3f s\n", ix, inf, walk,
+            reduce, red, t_format);
+}
+
+float pct(uint64_t a, uint64_t b) { return ((float)a / (float)b) * 100; }  // statistics.cpp:158: float32
+
+// decimal digits of v and one byte behind them into a buffer that is flushed when nearly full
+struct TsvWriter {
+    FILE *f;
+    std::vector<char> buf;
+    size_t used = 0;
+    bool ok = true;
+    explicit TsvWriter(FILE *file) : f(file), buf(1 << 20) {}
+    void flush() {
+        if (used && ok) ok = fwrite(buf.data(), 1, used, f) == used;
+        used = 0;
+    }
+    void room(size_t need) {
+        if (used + need > buf.size()) flush();
+    }
+    void text(const char *s, size_t n) {
+        if (n > buf.size()) {
+            flush();
+            if (ok) ok = fwrite(s, 1, n, f) == n;
+            return;
+        }
+        room(n);
+        memcpy(buf.data() + used, s, n);
+        used += n;
+    }
+    void number(uint64_t v, char end) {
+        room(24);
+        char tmp[24];
+        int k = 0;
+        do tmp[k++] = (char)('0' + v % 10);
+        while (v /= 10);
+        while (k) buf[used++] = tmp[--k];
+        buf[used++] = end;
+    }
+};
+
+}  // namespace
+
+int stats_bam_file(ChainContext &cc, const std::string &path, bool inserts, bool lengths) {
+    void *dz = nullptr;
+    uint64_t zb = 0;
+    if (upload_bam(cc, path, &dz, &zb)) {
+        if (dz) oge_dev_free(cc.ctx, dz);
+        return -1;
+    }
+    oge_bam_stats s;
+    const uint32_t *d_len = nullptr;
+    const uint64_t *d_cnt = nullptr;
+    std::vector<uint32_t> len;
+    std::vector<uint64_t> cnt;
+    int rc = oge_bam_stats_dev(cc.ctx, (const uint8_t *)dz, zb, (inserts ? OGE_STATS_INSERTS : 0) | (lengths ? OGE_STATS_LENGTHS : 0), &s,
+                               &d_len, &d_cnt);
+    if (!rc && lengths && s.n_lengths) {
+        len.resize(s.n_lengths);
+        cnt.resize(s.n_lengths);
+        rc = oge_memcpy(cc.ctx, len.data(), d_len, s.n_lengths * 4, 2);
+        if (!rc) rc = oge_memcpy(cc.ctx, cnt.data(), d_cnt, s.n_lengths * 8, 2);
+    }
+    oge_dev_free(cc.ctx, dz);
+    if (rc) return cc.fail("stats");
+    const auto t0 = clk();
+    auto line = [](const char *label, uint64_t v, uint64_t of) {
+        printf("%s%10llu (%5.1f%%)\n", label, (unsigned long long)v, (double)pct(v, of));
+    };
+    printf("Total reads:       %10llu\n", (unsigned long long)s.reads);
+    line("Mapped reads:      ", s.mapped, s.reads);
+    line("Forward strand:    ", s.forward, s.reads);
+    line("Reverse strand:    ", s.reverse, s.reads);
+    line("Failed QC:         ", s.failed_qc, s.reads);
+    line("Duplicates:        ", s.duplicates, s.reads);
+    line("Paired-end reads:  ", s.paired, s.reads);
+    if (s.paired) {
+        line("'Proper-pairs':    ", s.proper_pair, s.paired);
+        line("Both pairs mapped: ", s.both_mapped, s.paired);
+        printf("Read 1:            %10llu\n", (unsigned long long)s.read1);
+        printf("Read 2:            %10llu\n", (unsigned long long)s.read2);
+        line("Singletons:        ", s.singletons, s.paired);
+    }
+    printf("Sorted:            %10s\n", s.sorted ? "Yes" : "No");
+    if (lengths) {
+        fflush(stdout);
+        fprintf(stderr, "Read lengths:\n");
+        for (size_t k = 0; k < len.size(); ++k) {
+            const float p = (float)(100. * (double)cnt[k] / (double)s.reads);  // statistics.cpp:180
+            printf(" %5d" "bp:          %10llu (%5.1f%%)\n", (int)len[k], (unsigned long long)cnt[k], (double)p);
+        }
+    }
+    if (inserts) {
+        printf("Insert size (absolute value):\n");
+        if (s.n_insert) {
+            printf("    Mean:          %10.1f\n", (double)s.insert_sum / (double)s.n_insert);
+            const double median = s.n_insert % 2 ? (double)s.insert_mid_hi : ((double)s.insert_mid_hi + (double)s.insert_mid_lo) / 2.0;
+            printf("    Median:        %10.1f\n", median);
+        }
+    }
+    const bool ok = fflush(stdout) == 0 && !ferror(stdout);
+    report_stages(cc, "qc_stats", sec(t0, clk()));
+    if (!ok) {
+        fprintf(stderr, "openge: error writing to stdout\n");
+        return -1;
+    }
+    return 0;
+}
+
+int count_bam_file(ChainContext &cc, const std::string &path) {
+    void *dz = nullptr;
+    uint64_t zb = 0, n = 0;
+    if (upload_bam(cc, path, &dz, &zb)) {
+        if (dz) oge_dev_free(cc.ctx, dz);
+        return -1;
+    }
+    const int rc = oge_bam_count_dev(cc.ctx, (const uint8_t *)dz, zb, &n);
+    oge_dev_free(cc.ctx, dz);
+    if (rc) return cc.fail("count");
+    printf("%llu\n", (unsigned long long)n);
+    if (fflush(stdout) != 0 || ferror(stdout)) {
+        fprintf(stderr, "openge: error writing to stdout\n");
+        return -1;
+    }
+    return 0;
+}
+
+int coverage_bam_file(ChainContext &cc, const std::string &path, const std::string &out, int binsize, bool omit_uncovered) {
+    void *dz = nullptr;
+    uint64_t zb = 0, nb = 0, skipped = 0;
+    if (upload_bam(cc, path, &dz, &zb)) {
+        if (dz) oge_dev_free(cc.ctx, dz);
+        return -1;
+    }
+    const uint32_t *d_bins = nullptr;
+    int32_t overflow = 0, n_ref = 0;
+    const char *names = nullptr;
+    const int32_t *lens = nullptr;
+    uint64_t names_bytes = 0;
+    std::vector<uint32_t> bins;
+    int rc = oge_bam_coverage_dev(cc.ctx, (const uint8_t *)dz, zb, binsize, &d_bins, &nb, &skipped, &overflow);
+    oge_dev_free(cc.ctx, dz);
+    if (!rc) rc = oge_ctx_last_refs(cc.ctx, &n_ref, &names, &names_bytes, &lens);
+    if (!rc && nb) {
+        bins.resize(nb);
+        rc = oge_memcpy(cc.ctx, bins.data(), d_bins, nb * 4, 2);
+    }
+    if (rc) return cc.fail("coverage");
+    const auto t0 = clk();
+    std::vector<uint64_t> base((size_t)n_ref + 1);
+    oge_coverage_layout(n_ref, lens, binsize, base.data());
+    // the reference keeps its contigs in a std::map: bytewise name order, not header order
+    std::vector<std::pair<std::string, int32_t>> order;
+    const char *p = names;
+    for (int32_t r = 0; r < n_ref; ++r) {
+        order.emplace_back(p, r);
+        p += order.back().first.size() + 1;
+    }
+    std::sort(order.begin(), order.end());
+    if (skipped) fprintf(stderr, "Skipped %llu unmapped reads.\n", (unsigned long long)skipped);
+    fprintf(stderr, "Average coverage:\n");
+    for (auto &c : order) {
+        uint64_t total = 0;
+        for (uint64_t i = base[c.second]; i < base[c.second + 1]; ++i) total += bins[i];
+        fprintf(stderr, "   %20s: %8gx\n", c.first.c_str(), (double)total / lens[c.second]);
+    }
+    if (out != "stdout") {
+        FILE *f = fopen(out.c_str(), "wb");
+        bool ok = f != nullptr;
+        if (ok) {
+            TsvWriter w(f);
+            static const char head[] = "chromosome\tposition\tcoverage\n";
+            w.text(head, sizeof head - 1);
+            for (auto &c : order) {
+                const uint32_t *b = bins.data() + base[c.second];
+                const uint64_t m = base[c.second + 1] - base[c.second];
+                const std::string row = c.first + "\t";
+                for (uint64_t i = 0; i < m; ++i) {
+                    if (omit_uncovered && !b[i]) continue;
+                    w.text(row.data(), row.size());
+                    w.number((uint64_t)binsize * i + 1, '\t');
+                    w.number(b[i], '\n');
+                }
+            }
+            w.flush();
+            ok = w.ok;
+        }
+        if ((f && fclose(f) != 0) || !ok) {
+            fprintf(stderr, "openge: error writing %s: %s\n", out.c_str(), strerror(errno));
+            remove(out.c_str());
+            return -1;
+        }
+    }
+    if (overflow) fprintf(stderr, "Error: at least one overflow occurred when measuring coverage- try reducing binsizes.\n");
+    report_stages(cc, "qc_coverage", sec(t0, clk()));
+    return 0;
+}
+
 }  // namespace oge

@@ -222,4 +222,12 @@ protected:
 // `openge index in.bam [-o out.bai]`: the file into HBM, oge_bam_index_dev, the image to out (in.bam.bai)
 int index_bam_file(ChainContext &cc, const std::string &path, const std::string &out);
 
+// `openge stats [-I] [-L] in.bam`, `openge count in.bam`, `openge coverage [-o out.tsv] [-b N]
+// [--omituncoveredbases] in.bam`: the file into HBM, one whole-file call (oge_bam_stats_dev /
+// oge_bam_count_dev / oge_bam_coverage_dev), the reference's text formatted on the host
+// (algorithms/statistics.cpp:157-201, algorithms/measure_coverage.cpp:128-181)
+int stats_bam_file(ChainContext &cc, const std::string &path, bool inserts, bool lengths);
+int count_bam_file(ChainContext &cc, const std::string &path);
+int coverage_bam_file(ChainContext &cc, const std::string &path, const std::string &out, int binsize, bool omit_uncovered);
+
 }  // namespace oge

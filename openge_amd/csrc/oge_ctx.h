@@ -59,6 +59,11 @@ struct oge_ctx {
     uint64_t infl_clean_bytes = 0, infl_clean_next = 0;
     const uint8_t *bai_ptr = nullptr;  // the index image of the last call that built one (workspace "bai_image")
     uint64_t bai_bytes = 0;
+    // the binary reference list of the BAM file the last oge_bam_stats_dev / _coverage_dev / _count_dev call
+    // parsed (oge_ctx_last_refs): names NUL-terminated one after the other
+    bool refs_valid = false;
+    std::string ref_names;
+    std::vector<int32_t> ref_lens;
     std::map<std::string, uint64_t> counters;  // per call: work counts a stage reports (oge_ctx_counter)
     bool last_scan_generic = false;  // realign scan fell back to the byte-wise kernel
     double scan_t[3] = {0, 0, 0};    // realign scan host timings: validate, upload, device + download
@@ -159,6 +164,14 @@ int oge_bai_build_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_of
 // file offsets of the indexed blocks of d_z (nblk + 1 entries, workspace "bai_cstart"): cstart[nblk] = the end
 // of the last one; the oge_bai_build_impl call that consumes the table releases it
 int oge_bai_cstart(oge_ctx *ctx, const uint8_t *d_z, const uint64_t *d0, const uint64_t *d1, uint64_t nblk, uint64_t **cstart_out);
+
+// ---- stats / coverage (qc.hip) ----
+// oge_stats_dev / oge_coverage_dev without the context checks and the timing reset (the whole-file entry
+// points call them under their own hold)
+int oge_qc_stats_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, uint32_t want, oge_bam_stats *out,
+                      const uint32_t **d_len, const uint64_t **d_len_count);
+int oge_qc_coverage_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref, const int32_t *ref_len,
+                         int32_t binsize, const uint32_t **d_bins, uint64_t *n_skipped, int32_t *overflow);
 
 // ---- multi-GPU internals (dist.hip)
 oge_ctx *oge_comm_ctx(oge_comm *comm);

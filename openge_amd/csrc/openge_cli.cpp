@@ -3,6 +3,9 @@
 // dedup and localrealign, with the reference's option names and defaults.  Each command builds the
 // same module chain the reference builds (commands/command_mergesort.cpp:68-117,
 // command_dedup.cpp:48-69, command_localrealign.cpp:37-75) out of the modules in modules.h.
+// `index`, `stats`, `count` and `coverage` are one whole-file device call each (index_bam_file,
+// stats_bam_file, count_bam_file, coverage_bam_file in modules.cpp; commands/command_stats.cpp,
+// command_count.cpp, command_coverage.cpp for the last three).
 //
 // Deliberate differences: dedup defaults to `-v --nosplit` semantics (Q1, Q3).
 // --compat-nonverbose-dedup reproduces the non-verbose index bug; --split-chains K reproduces K
@@ -45,6 +48,9 @@ const Opt kMergesort[] = {{"o", "out", true}, {"r", "region", true},  {"q", "map
                           {"M", "markduplicates", false}, {"R", "removeduplicates", false}, {"", "index", false}};
 const Opt kDedup[] = {{"o", "out", true}, {"r", "remove", false}, {"", "index", false}};
 const Opt kIndex[] = {{"o", "out", true}};
+const Opt kStats[] = {{"I", "inserts", false}, {"L", "lengths", false}};
+const Opt kCoverage[] = {{"o", "out", true}, {"b", "binsize", true}, {"", "omituncoveredbases", false},
+                         {"V", "verifymapping", false}, {"S", "strict", false}};
 const Opt kRealign[] = {{"o", "out", true}, {"R", "reference", true}, {"L", "intervals", true}};
 
 struct Parsed {
@@ -104,9 +110,14 @@ bool parse(int argc, const char **argv, const std::vector<Opt> &opts, Parsed &p)
 }
 
 void usage_top() {
-    fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, index, version\n"
+    fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, index, stats, count, coverage,\n"
+                    "          version\n"
                     "\n    openge index in.bam [-o out.bai]    BAM index of a coordinate-sorted file (default in.bam.bai)\n"
                     "    mergesort / sort / dedup --index    also write <out>.bai (one GPU, file output, coordinate order)\n"
+                    "    openge stats [-I] [-L] in.bam       flag counts, Sorted: Yes/No, insert sizes (-I), read lengths (-L)\n"
+                    "    openge count in.bam                 the number of reads\n"
+                    "    openge coverage [-o out.tsv] [-b N] [--omituncoveredbases] in.bam\n"
+                    "                                        depth per bin of N bases (default 100); one file, one GPU\n"
                     "\nGPU options (every command):\n"
                     "    --device N              first GPU\n"
                     "    --gpus G                ranks over G GPUs\n"
@@ -136,6 +147,9 @@ int main(int argc, const char **argv) {
     else if (cmd == "dedup") opts.insert(opts.end(), std::begin(kDedup), std::end(kDedup));
     else if (cmd == "localrealign") opts.insert(opts.end(), std::begin(kRealign), std::end(kRealign));
     else if (cmd == "index") opts.insert(opts.end(), std::begin(kIndex), std::end(kIndex));
+    else if (cmd == "stats") opts.insert(opts.end(), std::begin(kStats), std::end(kStats));
+    else if (cmd == "count") ;  // no options of its own (commands/command_count.cpp)
+    else if (cmd == "coverage") opts.insert(opts.end(), std::begin(kCoverage), std::end(kCoverage));
     else {
         fprintf(stderr, "Unknown command %s.\n", argv[1]);
         return -1;
@@ -187,6 +201,26 @@ int main(int argc, const char **argv) {
         fprintf(stderr, "openge index: one BAM file is required\n");
         return -1;
     }
+    const bool qc = cmd == "stats" || cmd == "count" || cmd == "coverage";
+    if (qc) {  // refused before anything is read
+        const char *c = cmd.c_str();
+        if (p.inputs.size() != 1 || p.inputs[0] == "stdin" || p.inputs[0] == "-") {
+            fprintf(stderr, "openge %s: one BAM file is required\n", c);
+            return -1;
+        }
+        if (cc.gpus > 1) {
+            fprintf(stderr, "openge %s: --gpus is not provided\n", c);
+            return -1;
+        }
+        if (p.count("verifymapping") || p.count("strict")) {
+            fprintf(stderr, "openge coverage: -V/--verifymapping and -S/--strict are not provided\n");
+            return -1;
+        }
+        if (cmd == "coverage" && atoi(p.get("binsize", "100").c_str()) < 1) {
+            fprintf(stderr, "openge coverage: --binsize must be at least 1\n");
+            return -1;
+        }
+    }
     timeval t0;
     gettimeofday(&t0, nullptr);
     // one input file on one GPU: its bytes come off the disk / page cache while HIP initialises
@@ -202,6 +236,14 @@ int main(int argc, const char **argv) {
     }
     if (cmd == "index") {
         const int r = index_bam_file(cc, p.inputs[0], p.get("out", p.inputs[0] + ".bai"));
+        oge_ctx_destroy(cc.ctx);
+        return r;
+    }
+    if (qc) {
+        const int r = cmd == "stats"   ? stats_bam_file(cc, p.inputs[0], p.count("inserts"), p.count("lengths"))
+                      : cmd == "count" ? count_bam_file(cc, p.inputs[0])
+                                       : coverage_bam_file(cc, p.inputs[0], p.get("out", "stdout"), atoi(p.get("binsize", "100").c_str()),
+                                                           p.count("omituncoveredbases"));
         oge_ctx_destroy(cc.ctx);
         return r;
     }

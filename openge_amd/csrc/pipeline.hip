@@ -319,6 +319,73 @@ extern "C" int oge_bam_index_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbyt
     return oge_bai_build_impl(ctx, X, xoff, n, (int32_t)f.ref_names.size(), rec_base, ix.uoff, cstart, ix.nblk, d_bai, bai_bytes);
 }
 
+// stats / coverage / count of a whole BAM file resident in HBM: the reader half of the chain, then the
+// reduction over the records where they lie in the decompressed stream (qc.hip).  The file's reference list
+// stays with the context for oge_ctx_last_refs.
+static int decode_for_qc(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint8_t **X, uint64_t **xoff, uint64_t *n, BamFile *f) {
+    ctx->refs_valid = false;
+    uint64_t cap;
+    const int rc = decode(ctx, d_z, zbytes, X, &cap, xoff, n, f);
+    if (rc) return rc;
+    ctx->ref_names.clear();
+    for (const std::string &s : f->ref_names) ctx->ref_names.append(s.c_str(), s.size() + 1);
+    ctx->ref_lens = f->ref_lens;
+    ctx->refs_valid = true;
+    return OGE_OK;
+}
+
+extern "C" int oge_bam_stats_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint32_t want, oge_bam_stats *stats,
+                                 const uint32_t **d_len, const uint64_t **d_len_count) {
+    if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
+    if (!stats || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
+    (void)hipSetDevice(ctx->device);
+    Hold hold(ctx);
+    uint8_t *X;
+    uint64_t *xoff, n;
+    BamFile f;
+    const int rc = decode_for_qc(ctx, d_z, zbytes, &X, &xoff, &n, &f);
+    if (rc) return rc;
+    return oge_qc_stats_impl(ctx, X, xoff, n, want, stats, d_len, d_len_count);
+}
+
+extern "C" int oge_bam_coverage_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, int32_t binsize, const uint32_t **d_bins,
+                                    uint64_t *n_bins, uint64_t *n_skipped, int32_t *overflow) {
+    if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
+    if (!d_bins || !n_bins || !n_skipped || !overflow || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
+    if (binsize < 1) return oge_fail(ctx, OGE_ERR_ARG, "coverage: binsize < 1");
+    (void)hipSetDevice(ctx->device);
+    Hold hold(ctx);
+    *d_bins = nullptr;
+    *n_bins = 0;
+    uint8_t *X;
+    uint64_t *xoff, n;
+    BamFile f;
+    int rc = decode_for_qc(ctx, d_z, zbytes, &X, &xoff, &n, &f);
+    if (rc) return rc;
+    std::vector<std::string> names = f.ref_names;
+    std::sort(names.begin(), names.end());
+    const auto dup = std::adjacent_find(names.begin(), names.end());
+    if (dup != names.end()) return oge_fail(ctx, OGE_ERR_ARG, ("coverage: two contigs are named " + *dup).c_str());
+    const int32_t n_ref = (int32_t)f.ref_lens.size();
+    std::vector<uint64_t> base((size_t)n_ref + 1);
+    rc = oge_coverage_layout(n_ref, f.ref_lens.data(), binsize, base.data());
+    if (rc) return oge_fail(ctx, rc, "coverage: layout");
+    rc = oge_qc_coverage_impl(ctx, X, xoff, n, n_ref, f.ref_lens.data(), binsize, d_bins, n_skipped, overflow);
+    if (!rc) *n_bins = base[n_ref];
+    return rc;
+}
+
+extern "C" int oge_bam_count_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint64_t *n_reads) {
+    if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
+    if (!n_reads || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
+    (void)hipSetDevice(ctx->device);
+    Hold hold(ctx);
+    uint8_t *X;
+    uint64_t *xoff;
+    BamFile f;
+    return decode_for_qc(ctx, d_z, zbytes, &X, &xoff, n_reads, &f);  // the record walk's count
+}
+
 // The same chain on a BAM file in HOST memory with the PCIe transfers overlapped (the
 // reference's reader / writer threads overlap I/O with the modules, util/bgzf_input_stream.cpp:180-206,
 // util/bgzf_output_stream.cpp:252-285): the file goes up in G chunks on a copy stream while the host

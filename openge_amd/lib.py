@@ -50,6 +50,18 @@ class FilterOpts(C.Structure):
                                          "max_len", "trim_total")] + [("count_limit", C.c_uint64)]
 
 
+class BamStats(C.Structure):
+    """Mirror of oge_bam_stats (include/openge_hip.h)."""
+
+    COUNTERS = ("reads", "mapped", "forward", "reverse", "failed_qc", "duplicates", "paired", "proper_pair", "read1", "read2",
+                "both_mapped", "singletons")
+    _fields_ = ([(k, C.c_uint64) for k in COUNTERS] + [("sorted", C.c_int32), ("pad0", C.c_int32)] +
+                [(k, C.c_uint64) for k in ("n_insert", "insert_sum", "insert_mid_lo", "insert_mid_hi", "n_lengths")])
+
+
+STATS_INSERTS, STATS_LENGTHS = 1, 2
+
+
 class MergesortOpts(C.Structure):
     """Mirror of oge_mergesort_opts (include/openge_hip.h)."""
 
@@ -279,6 +291,15 @@ def lib() -> C.CDLL:
         "oge_bai_build": (C.c_int, [vp, vp, u64, vp, u64, i32, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]),
         "oge_bam_index_dev": (C.c_int, [vp, vp, u64, C.POINTER(vp), C.POINTER(u64)]),
         "oge_ctx_last_bai": (C.c_int, [vp, C.POINTER(vp), C.POINTER(u64)]),
+        "oge_stats_dev": (C.c_int, [vp, vp, vp, u64, u32, vp, C.POINTER(vp), C.POINTER(vp)]),
+        "oge_stats": (C.c_int, [vp, vp, u64, vp, u64, u32, vp, vp, vp, u64]),
+        "oge_coverage_layout": (C.c_int, [i32, vp, i32, vp]),
+        "oge_coverage_dev": (C.c_int, [vp, vp, vp, u64, i32, vp, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(i32)]),
+        "oge_coverage": (C.c_int, [vp, vp, u64, vp, u64, i32, vp, i32, vp, u64, C.POINTER(u64), C.POINTER(i32)]),
+        "oge_bam_stats_dev": (C.c_int, [vp, vp, u64, u32, vp, C.POINTER(vp), C.POINTER(vp)]),
+        "oge_bam_coverage_dev": (C.c_int, [vp, vp, u64, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]),
+        "oge_bam_count_dev": (C.c_int, [vp, vp, u64, C.POINTER(u64)]),
+        "oge_ctx_last_refs": (C.c_int, [vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp)]),
         "oge_mergesort_opts_init": (None, [vp]),
         "oge_mergesort_bgzf_dev": (C.c_int, [vp, vp, u64, vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64),
                                              C.POINTER(u64)]),
@@ -616,6 +637,121 @@ class Context:
         d, nb = C.c_void_p(), C.c_uint64()
         check(lib().oge_ctx_last_bai(self.h, C.byref(d), C.byref(nb)), self.h)
         return self._fetch(d.value, nb.value)
+
+    # ---- stats / count / coverage (csrc/qc.hip)
+    def _stats_dict(self, st: BamStats, d_len, d_cnt, lengths: bool) -> dict:
+        out = {k: getattr(st, k) for k in BamStats.COUNTERS}
+        out["sorted"] = bool(st.sorted)
+        for k in ("n_insert", "insert_sum", "insert_mid_lo", "insert_mid_hi"):
+            out[k] = getattr(st, k)
+        if lengths:
+            m = st.n_lengths
+            out["lengths"] = (np.frombuffer(self._fetch(d_len.value or 0, 4 * m), np.uint32).copy(),
+                              np.frombuffer(self._fetch(d_cnt.value or 0, 8 * m), np.uint64).copy())
+        return out
+
+    @staticmethod
+    def _want(inserts: bool, lengths: bool) -> int:
+        return (STATS_INSERTS if inserts else 0) | (STATS_LENGTHS if lengths else 0)
+
+    def stats_dev(self, d_recs, d_off, n: int, inserts: bool = False, lengths: bool = False) -> dict:
+        """oge_stats_dev on device records (d_off: n offsets) -> the counters, `sorted`, the insert figures and,
+        with lengths, `lengths` = (l_seq values ascending, their counts)."""
+        st, dl, dc = BamStats(), C.c_void_p(), C.c_void_p()
+        check(lib().oge_stats_dev(self.h, d_recs, d_off, n, self._want(inserts, lengths), C.byref(st), C.byref(dl), C.byref(dc)), self.h)
+        return self._stats_dict(st, dl, dc, lengths)
+
+    def stats(self, recs: np.ndarray, offs: np.ndarray, n: int, inserts: bool = False, lengths: bool = False) -> dict:
+        """oge_stats: the same from host buffers."""
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        st = BamStats()
+        args = (self.h, _ptr(recs), recs.nbytes, _ptr(offs), n, self._want(inserts, lengths), C.byref(st))
+        rc = lib().oge_stats(*args, None, None, 0)
+        if not (rc == -3 and lengths and st.n_lengths):  # OGE_ERR_LIMIT with the size: the sizing call
+            check(rc, self.h)
+        ln, ct = np.empty(max(st.n_lengths, 1), np.uint32), np.empty(max(st.n_lengths, 1), np.uint64)
+        if rc:
+            check(lib().oge_stats(*args, _ptr(ln), _ptr(ct), len(ln)), self.h)
+        out = self._stats_dict(st, C.c_void_p(), C.c_void_p(), False)
+        if lengths:
+            out["lengths"] = (ln[:st.n_lengths], ct[:st.n_lengths])
+        return out
+
+    @staticmethod
+    def coverage_layout(ref_len, binsize: int) -> np.ndarray:
+        """oge_coverage_layout: base[r] = the bins in front of contig r (n_ref + 1 entries)."""
+        lens = np.ascontiguousarray(ref_len, dtype=np.int32)
+        base = np.zeros(len(lens) + 1, np.uint64)
+        check(lib().oge_coverage_layout(len(lens), _ptr(lens) if len(lens) else None, binsize, _ptr(base)))
+        return base
+
+    def coverage_dev(self, d_recs, d_off, n: int, ref_len, binsize: int = 100, fetch: bool = True):
+        """oge_coverage_dev on device records -> (bins u32 in header order, skipped reads, overflow); with
+        fetch=False the bins stay on the device: (device pointer, number of bins, skipped reads, overflow)."""
+        lens = np.ascontiguousarray(ref_len, dtype=np.int32)
+        d, sk, ov = C.c_void_p(), C.c_uint64(), C.c_int32()
+        check(lib().oge_coverage_dev(self.h, d_recs, d_off, n, len(lens), _ptr(lens) if len(lens) else None, binsize, C.byref(d),
+                                     C.byref(sk), C.byref(ov)), self.h)
+        nb = int(self.coverage_layout(lens, binsize)[-1])
+        if not fetch:
+            return d.value or 0, nb, sk.value, bool(ov.value)
+        return np.frombuffer(self._fetch(d.value or 0, 4 * nb), np.uint32).copy(), sk.value, bool(ov.value)
+
+    def coverage(self, recs: np.ndarray, offs: np.ndarray, n: int, ref_len, binsize: int = 100) -> tuple[np.ndarray, int, bool]:
+        """oge_coverage: the same from host buffers."""
+        lens = np.ascontiguousarray(ref_len, dtype=np.int32)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nb = int(self.coverage_layout(lens, binsize)[-1])
+        bins, sk, ov = np.zeros(max(nb, 1), np.uint32), C.c_uint64(), C.c_int32()
+        check(lib().oge_coverage(self.h, _ptr(recs), recs.nbytes, _ptr(offs), n, len(lens), _ptr(lens) if len(lens) else None, binsize,
+                                 _ptr(bins), nb, C.byref(sk), C.byref(ov)), self.h)
+        return bins[:nb], sk.value, bool(ov.value)
+
+    def _with_file(self, data: bytes, fn):
+        a = np.frombuffer(data, dtype=np.uint8)
+        dz = C.c_void_p()
+        check(lib().oge_dev_alloc(self.h, len(a) + 64, C.byref(dz)), self.h)
+        try:
+            check(lib().oge_memcpy(self.h, dz, _ptr(a), len(a), 1), self.h)
+            return fn(dz, len(a))
+        finally:
+            lib().oge_dev_free(self.h, dz)
+
+    def last_refs(self) -> tuple[list[str], np.ndarray]:
+        """oge_ctx_last_refs: names and lengths of the file the last whole-file stats / coverage / count call read."""
+        n, p, nb, pl = C.c_int32(), C.c_void_p(), C.c_uint64(), C.c_void_p()
+        check(lib().oge_ctx_last_refs(self.h, C.byref(n), C.byref(p), C.byref(nb), C.byref(pl)), self.h)
+        names = C.string_at(p.value, nb.value).split(b"\0")[:n.value] if nb.value else []
+        lens = np.frombuffer(C.string_at(pl.value, 4 * n.value), np.int32).copy() if n.value else np.zeros(0, np.int32)
+        return [x.decode() for x in names], lens
+
+    def bam_stats(self, data: bytes, inserts: bool = False, lengths: bool = False) -> dict:
+        """`openge stats` of a whole BAM file (oge_bam_stats_dev on a copy of the file in HBM)."""
+        def run(dz, nbytes):
+            st, dl, dc = BamStats(), C.c_void_p(), C.c_void_p()
+            check(lib().oge_bam_stats_dev(self.h, dz, nbytes, self._want(inserts, lengths), C.byref(st), C.byref(dl), C.byref(dc)),
+                  self.h)
+            return self._stats_dict(st, dl, dc, lengths)
+        return self._with_file(data, run)
+
+    def bam_coverage(self, data: bytes, binsize: int = 100):
+        """`openge coverage` of a whole BAM file -> (names, lens, base, bins, n_skipped, overflow); bins in header
+        order, contig r at bins[base[r]:base[r + 1]]."""
+        def run(dz, nbytes):
+            d, nb, sk, ov = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_int32()
+            check(lib().oge_bam_coverage_dev(self.h, dz, nbytes, binsize, C.byref(d), C.byref(nb), C.byref(sk), C.byref(ov)), self.h)
+            bins = np.frombuffer(self._fetch(d.value or 0, 4 * nb.value), np.uint32).copy()
+            names, lens = self.last_refs()
+            return names, lens, self.coverage_layout(lens, binsize), bins, sk.value, bool(ov.value)
+        return self._with_file(data, run)
+
+    def bam_count(self, data: bytes) -> int:
+        """`openge count`: the number of records of a whole BAM file (oge_bam_count_dev)."""
+        def run(dz, nbytes):
+            n = C.c_uint64()
+            check(lib().oge_bam_count_dev(self.h, dz, nbytes, C.byref(n)), self.h)
+            return n.value
+        return self._with_file(data, run)
 
     def mem_info(self) -> tuple[int, int]:
         f, t = C.c_uint64(), C.c_uint64()
