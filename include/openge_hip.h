@@ -554,6 +554,54 @@ int oge_bam_count_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint64_
  * there is none. */
 int oge_ctx_last_refs(oge_ctx *ctx, int32_t *n_ref, const char **names, uint64_t *names_bytes, const int32_t **ref_len);
 
+/* ---- SAM and FASTQ text of records in HBM (openge view, -F sam|fastq) ----------------------------------
+ * The reference's SamWriter::write (util/sam_writer.cpp:90-217) and the single-stream form of
+ * FastqWriter::write (util/fastq_writer.cpp:99-100) on the device; DESIGN.md section 21.
+ * SAM line: QNAME FLAG RNAME POS+1 MAPQ CIGAR, the mate fields, SEQ, QUAL, the tags, tab separated, "\n".
+ * RNAME is "*" when refID is outside [0, n_ref); CIGAR "*" without ops (letters MIDNSHP=X, '?' for codes 9-15);
+ * the mate fields are ("=" | the mate's contig) MPOS+1 TLEN when FLAG 0x1 is set and 0 <= mate refID < n_ref,
+ * else "*" 0 0; SEQ from the 4-bit codes by "=ACMGRSVTWYHKDBN" and QUAL as byte + 33 (wrapping at 8 bits), both
+ * "*" when l_seq is 0; tags A, c C s S i I (all printed i:), Z and H in record order; a NUL byte behind a tag's
+ * value ends the tag list (sam_writer.cpp:210).  POS+1 and MPOS+1 are computed in 64 bits.
+ * FASTQ entry: "@" name "\n" SEQ "\n+" name "\n" QUAL "\n" with SEQ and QUAL cut to [trim_begin,
+ * l_seq - trim_end) (Filter::trim, algorithms/filter.cpp:183-190; empty when l_seq <= trim_begin + trim_end).
+ * SEQ under a trim window is the reference's; its QUAL is not reproduced: Filter::trim cuts the qualities of
+ * the read it has already shortened a second time, which leaves fewer qualities than bases, bytes from behind
+ * the qualities in reads without tags, and an abort on short reads.
+ * Records with an f or a B tag are formatted on the host (f as printf "%g", B as the SAM specification's
+ * XX:B:t,v,v with %g float elements; the reference's switch has no B case): the device marks them, gives
+ * them length 0 and leaves them out.  A record with any other tag type, with a tag or a Z string cut short,
+ * or whose lengths do not fit its block_size fails the size call with OGE_ERR_ARG naming the record index. */
+enum { OGE_TEXT_SAM = 0, OGE_TEXT_FASTQ = 1 };
+typedef struct oge_text_opts {
+    int32_t mode;                 /* OGE_TEXT_SAM / OGE_TEXT_FASTQ */
+    int32_t trim_begin, trim_end; /* FASTQ only, >= 0 */
+    int32_t n_ref;
+    const char *ref_names;        /* host: the n_ref contig names back to back, no separators */
+    const uint32_t *ref_name_off; /* host: n_ref + 1 offsets into ref_names */
+} oge_text_opts;
+/* Size pass and scan.  Records d_recs + d_off[i] (n offsets read; the arena carries 16 bytes of slack behind
+ * the last record).  d_text_off (n + 1 entries): the exclusive scan of the text lengths, 0 for marked records;
+ * d_host_mark (n bytes): 1 for a record the host formats, else 0.  *total = d_text_off[n], *n_host = the
+ * marked records, also the context counter "sam_host_lines".  The contig table is uploaded when it differs
+ * from the last call's.  OGE_ERR_LIMIT when n >= 2^32 - 1.  Stage name for oge_ctx_timing: "text_size". */
+int oge_text_size_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_text_opts *opts,
+                      uint64_t *d_text_off, uint8_t *d_host_mark, uint64_t *total, uint64_t *n_host);
+/* Emit pass: the text of records [first, first + count) at d_out + d_text_off[i] - d_text_off[first]; cap >=
+ * d_text_off[first + count] - d_text_off[first] (OGE_ERR_LIMIT otherwise, nothing is written).  opts and
+ * d_text_off as in the size call that filled d_text_off.  Counters "text_wave_records" / "text_block_records":
+ * the records one wave / one workgroup of the kernel takes.  Stage name: "text_emit". */
+int oge_text_emit_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, const uint64_t *d_text_off, uint64_t first,
+                      uint64_t count, const oge_text_opts *opts, uint8_t *d_out, uint64_t cap);
+/* One record's text on the host, every tag type included (the lines the device leaves out): written to buf
+ * when cap holds it, *len = its length (OGE_ERR_LIMIT when cap is smaller, with *len set).  rec_bytes =
+ * block_size + 4. */
+int oge_text_host_line(const uint8_t *rec, uint64_t rec_bytes, const oge_text_opts *opts, char *buf, uint64_t cap, uint64_t *len);
+/* Host-buffer form: uploads, sizes, emits, downloads and splices the host-formatted lines in at their places.
+ * *bytes = the whole text's length; OGE_ERR_LIMIT when cap is smaller (with *bytes set, nothing written). */
+int oge_text_format(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const uint64_t *rec_off, uint64_t n,
+                    const oge_text_opts *opts, uint8_t *out, uint64_t cap, uint64_t *bytes);
+
 /* ---- mergesort extras: Filter (-r region / -q mapq) and sort by name (-b) ----------- */
 /* Filter::runInternal's predicate (algorithms/filter.cpp:205-249) with the module's setters
  * (filter.h:34-47).  len = l_seq (BamAlignment::getLength).  A record is kept when

@@ -2,9 +2,11 @@
 #include "modules.h"
 
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <climits>
 #include <cstdio>
+#include <cstdlib>
 #include <cerrno>
 #include <cstring>
 #include <map>
@@ -1130,10 +1132,209 @@ int LocalRealignment::runInternal(ChainContext &cc, ReadBatch &b) {
 }
 
 // ----------------------------------------------------------------------------------- FileWriter
+FileFormat detect_file_format(std::string name) {
+    std::transform(name.begin(), name.end(), name.begin(), ::tolower);
+    auto ends = [&](const char *suffix) {
+        const size_t k = strlen(suffix);
+        return name.size() >= k && name.compare(name.size() - k, k, suffix) == 0;
+    };
+    if (ends("rawbam") || ends("bamraw")) return FORMAT_RAWBAM;
+    if (ends("bam")) return FORMAT_BAM;
+    if (ends("sam")) return FORMAT_SAM;
+    if (ends("cram")) return FORMAT_CRAM;
+    if (ends("fastq")) return FORMAT_FASTQ;
+    return FORMAT_UNKNOWN;
+}
+
 int FileWriter::setFormat(const std::string &f) {
-    if (f == "bam" || f == "BAM") return 0;
-    fprintf(stderr, "openge: output format %s is not provided (BAM only)\n", f.c_str());
-    return -1;
+    const FileFormat fmt = detect_file_format(f);
+    if (fmt == FORMAT_UNKNOWN) {  // file_writer.cpp:49-52
+        fprintf(stderr, "Unknown file format specified: %s. Aborting.\n", f.c_str());
+        return -1;
+    }
+    if (fmt == FORMAT_RAWBAM || fmt == FORMAT_CRAM) {
+        fprintf(stderr, "openge: output format %s is not provided (bam, sam or fastq)\n", f.c_str());
+        return -1;
+    }
+    format_ = fmt;
+    return 0;
+}
+
+FileFormat FileWriter::getFileFormat() const {
+    if (format_ != FORMAT_UNKNOWN) return format_;
+    if (!detect_from_name_) return FORMAT_BAM;
+    const FileFormat fmt = detect_file_format(filename_);
+    return fmt == FORMAT_UNKNOWN ? default_format_ : fmt;
+}
+
+// Device-resident records -> SAM or FASTQ text.  Everything that can fail on the records (an unknown tag
+// type, a host line that does not format) fails before the output is opened.
+int FileWriter::write_text(ChainContext &cc, ReadBatch &b, FileFormat fmt) {
+    auto clk = [] { return std::chrono::steady_clock::now(); };
+    auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point z) {
+        return std::chrono::duration<double>(z - a).count();
+    };
+    const bool to_stdout = filename_ == "stdout" || filename_ == "-";
+    const char *why = !b.slices.empty() ? "--gpus"
+                      : b.produce       ? "output larger than device memory (chunked sort)"
+                      : index_          ? "--index"
+                      : fmt == FORMAT_FASTQ && !to_stdout ? "FASTQ files (only -o stdout: the _1.fastq / _2.fastq / .fastq split is not provided)"
+                                        : nullptr;
+    if (why) {
+        fprintf(stderr, "openge: %s output is not provided with %s\n", fmt == FORMAT_SAM ? "SAM" : "FASTQ", why);
+        return -1;
+    }
+    const auto t0 = clk();
+    if (b.n && cc.to_device(b)) return -1;  // a batch that is only host-valid goes up first
+    uint8_t *recs = b.d_recs;
+    uint64_t *offs = b.d_offs;
+    uint64_t n = b.n;
+    void *kept = nullptr, *kept_off = nullptr, *d_toff = nullptr, *d_mark = nullptr, *d_out = nullptr, *hz[2] = {nullptr, nullptr};
+    std::thread wr;
+    auto release = [&]() {
+        if (wr.joinable()) wr.join();
+        for (void *p : {kept, kept_off, d_toff, d_mark, d_out})
+            if (p) oge_dev_free(cc.ctx, p);
+        for (void *h : hz)
+            if (h) oge_host_free(cc.ctx, h);
+    };
+    auto bail = [&](const char *what) {
+        release();
+        return cc.fail(what);
+    };
+    if (b.drop_duplicates && n) {
+        uint64_t m = 0;
+        if (oge_dev_alloc(cc.ctx, b.d_bytes + 64, &kept) || oge_dev_alloc(cc.ctx, (n + 1) * 8, &kept_off)) return bail("device allocation");
+        if (oge_drop_flagged_dev(cc.ctx, recs, offs, n, OGE_F_DUP, (uint8_t *)kept, (uint64_t *)kept_off, &m)) return bail("FileWriter: drop duplicates");
+        recs = (uint8_t *)kept;
+        offs = (uint64_t *)kept_off;
+        n = m;
+    }
+    std::string names;
+    std::vector<uint32_t> name_off{0};
+    for (auto &sq : b.header.sq) {
+        names += sq.name;
+        name_off.push_back((uint32_t)names.size());
+    }
+    oge_text_opts o;
+    o.mode = fmt == FORMAT_SAM ? OGE_TEXT_SAM : OGE_TEXT_FASTQ;
+    o.trim_begin = fmt == FORMAT_FASTQ ? trim_begin_ : 0;
+    o.trim_end = fmt == FORMAT_FASTQ ? trim_end_ : 0;
+    o.n_ref = (int32_t)b.header.sq.size();
+    o.ref_names = names.data();
+    o.ref_name_off = name_off.data();
+    uint64_t total = 0, n_host = 0;
+    if (oge_dev_alloc(cc.ctx, (n + 1) * 8, &d_toff) || oge_dev_alloc(cc.ctx, n + 1, &d_mark)) return bail("device allocation");
+    if (oge_text_size_dev(cc.ctx, recs, offs, n, &o, (uint64_t *)d_toff, (uint8_t *)d_mark, &total, &n_host)) return bail("FileWriter");
+    std::vector<uint64_t> toff(n + 1);
+    if (oge_memcpy(cc.ctx, toff.data(), d_toff, (n + 1) * 8, 2)) return bail("device->host copy");
+    // the lines the device leaves out, formatted here from the records' bytes
+    std::vector<uint64_t> host_rec;
+    std::vector<std::string> host_line;
+    if (n_host) {
+        std::vector<uint8_t> mark(n);
+        if (oge_memcpy(cc.ctx, mark.data(), d_mark, n, 2)) return bail("device->host copy");
+        std::vector<uint8_t> rb;
+        std::vector<char> line;
+        for (uint64_t i = 0; i < n; ++i) {
+            if (!mark[i]) continue;
+            uint64_t at = 0, len = 0;
+            uint32_t bs = 0;
+            if (oge_memcpy(cc.ctx, &at, offs + i, 8, 2) || oge_memcpy(cc.ctx, &bs, recs + at, 4, 2)) return bail("device->host copy");
+            rb.resize((size_t)bs + 4);
+            if (oge_memcpy(cc.ctx, rb.data(), recs + at, rb.size(), 2)) return bail("device->host copy");
+            line.resize(16 * rb.size() + 1024);
+            if (oge_text_host_line(rb.data(), rb.size(), &o, line.data(), line.size(), &len)) {
+                release();
+                fprintf(stderr, "openge: FileWriter: record %llu: %s\n", (unsigned long long)i, oge_last_error(nullptr));
+                return -1;
+            }
+            host_rec.push_back(i);
+            host_line.emplace_back(line.data(), (size_t)len);
+        }
+    }
+    // chunks of records whose text fits the chunk size (one record at least)
+    const char *ce = getenv("OGE_TEXT_CHUNK");
+    const uint64_t chunk = ce ? std::max<uint64_t>(1, strtoull(ce, nullptr, 10)) : (64ull << 20);
+    std::vector<uint64_t> cut{0};
+    uint64_t cap = 0;
+    while (cut.back() < n) {
+        const uint64_t s = cut.back();
+        uint64_t e = (uint64_t)(std::upper_bound(toff.begin() + s + 1, toff.end(), toff[s] + chunk) - toff.begin()) - 1;
+        if (e == s) e = s + 1;
+        cap = std::max(cap, toff[e] - toff[s]);
+        cut.push_back(e);
+    }
+    const size_t nchunks = cut.size() - 1;
+    if (cap && (oge_dev_alloc(cc.ctx, cap + 16, &d_out) || oge_host_alloc(cc.ctx, cap, &hz[0]) || (nchunks > 1 && oge_host_alloc(cc.ctx, cap, &hz[1]))))
+        return bail("FileWriter: buffers");
+    FILE *f = to_stdout ? stdout : fopen(filename_.c_str(), "wb");
+    if (!f) {
+        release();
+        fprintf(stderr, "Error opening %s file to write.\n", fmt == FORMAT_SAM ? "SAM" : "FASTQ");
+        return -1;
+    }
+    std::atomic<bool> failed(false);
+    auto put = [&failed, f](const void *p, size_t k) {
+        if (k && fwrite(p, 1, k, f) != k) failed = true;
+    };
+    if (fmt == FORMAT_SAM) {  // sam_writer.cpp:75-76: the regenerated header, with the @PG line unless --nopg
+        BamHeaderModel h = b.header;
+        if (!program_line_.empty()) add_program_record(h, program_line_);
+        const std::string text = h.to_string();
+        put(text.data(), text.size());
+    }
+    double t_dev = 0, t_d2h = 0, t_wait = 0;
+    size_t hk = 0;  // the next host line
+    int k = 0;
+    for (size_t c = 0; c < nchunks && !failed; ++c, k ^= 1) {
+        const uint64_t s = cut[c], e = cut[c + 1], bytes = toff[e] - toff[s];
+        auto t = clk();
+        if (oge_text_emit_dev(cc.ctx, recs, offs, (const uint64_t *)d_toff, s, e - s, &o, (uint8_t *)d_out, cap) || oge_ctx_sync(cc.ctx)) {
+            release();
+            if (f != stdout) fclose(f);
+            return cc.fail("FileWriter: text on the device");
+        }
+        t_dev += sec(t, clk());
+        t = clk();
+        if (wr.joinable()) wr.join();  // the buffer written two chunks ago is free again
+        t_wait += sec(t, clk());
+        t = clk();
+        if (bytes && oge_memcpy(cc.ctx, hz[k], d_out, bytes, 2)) {
+            release();
+            if (f != stdout) fclose(f);
+            return cc.fail("device->host copy");
+        }
+        t_d2h += sec(t, clk());
+        const size_t h0 = hk;
+        while (hk < host_rec.size() && host_rec[hk] < e) ++hk;
+        const size_t h1 = hk;
+        const uint8_t *hp = (const uint8_t *)hz[k];
+        wr = std::thread([&, hp, s, bytes, h0, h1]() {
+            uint64_t done = 0;
+            for (size_t j = h0; j < h1; ++j) {
+                const uint64_t at = toff[host_rec[j]] - toff[s];
+                put(hp + done, at - done);
+                done = at;
+                put(host_line[j].data(), host_line[j].size());
+            }
+            put(hp + done, bytes - done);
+        });
+    }
+    auto t = clk();
+    if (wr.joinable()) wr.join();
+    t_wait += sec(t, clk());
+    release();
+    if (f != stdout ? fclose(f) != 0 : fflush(f) != 0) failed = true;
+    if (failed) {
+        fprintf(stderr, "openge: error writing %s: %s\n", filename_.c_str(), strerror(errno));
+        return -1;
+    }
+    if (verbose_)
+        fprintf(stderr, "[openge] FileWriter: %s text %llu bytes in %zu chunks, %llu lines formatted on the host; size + emit %.3f s (gpu), "
+                "device->host %.3f s, waiting on the output %.3f s, total %.3f s\n", fmt == FORMAT_SAM ? "SAM" : "FASTQ",
+                (unsigned long long)total, nchunks, (unsigned long long)n_host, t_dev, t_d2h, t_wait, sec(t0, clk()));
+    return 0;
 }
 
 // the bin every record must carry (bam_serializer.h:112-116), recomputed in place by the workers
@@ -1416,6 +1617,12 @@ int FileWriter::runInternal(ChainContext &cc, ReadBatch &b) {
     auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point z) {
         return std::chrono::duration<double>(z - a).count();
     };
+    const FileFormat fmt = getFileFormat();
+    if (fmt == FORMAT_SAM || fmt == FORMAT_FASTQ) return write_text(cc, b, fmt);
+    if (fmt != FORMAT_BAM) {  // file_writer.cpp:192-195
+        fprintf(stderr, "Unsupported output file format selected. Aborting.\n");
+        return -1;
+    }
     const auto t0 = clk();
     const bool sliced = !b.slices.empty(), produced = (bool)b.produce;
     bool on_device = sliced || produced || (b.dev_valid && !b.host_valid && !bgzf_host_codec_forced());

@@ -126,9 +126,9 @@ protected:
 };
 
 // Filter (algorithms/filter.h:30-70, filter.cpp:185-249): mergesort's -r region / -q mapq, as a
-// device compaction (oge_filter_records_dev).  Trimming (setTrimBeginLength/EndLength) edits
-// records and is only reachable from the bpipe `filter` command, which is out of scope; its
-// length condition (len > trim total) is kept.
+// device compaction (oge_filter_records_dev).  Trimming (setTrimBeginLength/EndLength, `view -B/-E`)
+// drops the reads it would leave empty (len > trim total); the cut itself is made where the FASTQ text
+// is formatted (FileWriter::setTrim), the only format the reference allows it with.
 class Filter : public AlgorithmModule {
 public:
     Filter() : AlgorithmModule("Filter") { oge_filter_opts_init(&opts_); }
@@ -140,12 +140,15 @@ public:
     int getQualityLimit() const { return opts_.mapq_min; }
     void setMinimumReadLength(int l) { opts_.min_len = l; }
     void setMaximumReadLength(int l) { opts_.max_len = l; }
+    void setTrimBeginLength(int l) { trim_begin_ = l; opts_.trim_total = trim_begin_ + trim_end_; }
+    void setTrimEndLength(int l) { trim_end_ = l; opts_.trim_total = trim_begin_ + trim_end_; }
     bool setReadLengths(const std::string &s);  // "64", "64-72", "-64", "+64" (filter.cpp:150-183)
     uint64_t kept = 0;
 protected:
     int runInternal(ChainContext &cc, ReadBatch &b) override;
     std::string region_;
     bool has_region_ = false;
+    int trim_begin_ = 0, trim_end_ = 0;
     oge_filter_opts opts_;
 };
 
@@ -195,8 +198,12 @@ protected:
 // is cut into G contiguous input ranges, one per rank, and oge_sort_markdup_dist leaves b.slices.
 int run_ranks(ChainContext &cc, ReadBatch &b, bool sort, const oge_markdup_opts *opts, uint64_t *n_dup);
 
-// FileWriter (algorithms/file_writer.cpp:69-196): BAM output, @PG record unless --nopg, BGZF at the
-// given level, bin recomputed on every record.
+// FileWriter (algorithms/file_writer.cpp:45-196): BAM output, @PG record unless --nopg, BGZF at the
+// given level, bin recomputed on every record; SAM text, and FASTQ text to stdout, formatted on the device
+// (write_text).  The reference's RAWBAM and CRAM formats, and FASTQ to files, are refused.
+enum FileFormat { FORMAT_BAM, FORMAT_RAWBAM, FORMAT_SAM, FORMAT_CRAM, FORMAT_FASTQ, FORMAT_UNKNOWN };
+// detectFileFormatFromFilename (util/file_io.h:30-47): by the lower-cased name's suffix
+FileFormat detect_file_format(std::string name);
 class FileWriter : public AlgorithmModule {
 public:
     FileWriter() : AlgorithmModule("FileWriter") {}
@@ -206,7 +213,18 @@ public:
     int write_slices(ChainContext &cc, ReadBatch &b, BgzfWriter &w);
     int write_ranges(ChainContext &cc, ReadBatch &b, BgzfWriter &w);
     void addProgramLine(const std::string &cl) { program_line_ = cl; }
-    int setFormat(const std::string &f);  // only "bam" is supported (SAM/FASTQ out of scope)
+    // -F: "bam", "sam" or "fastq" as detect_file_format reads them; anything else prints the reference's
+    // message and returns -1
+    int setFormat(const std::string &f);
+    // `view`: with no -F the output name's suffix decides, then this default (file_writer.cpp:57-67); the other
+    // commands write BAM whatever the name
+    void setDefaultFormat(FileFormat f) { default_format_ = f; detect_from_name_ = true; }
+    FileFormat getFileFormat() const;
+    void setTrim(int begin, int end) { trim_begin_ = begin; trim_end_ = end; }  // FASTQ: bases cut from both ends
+    // SAM / FASTQ: size pass and scan once, then the emit pass chunk by chunk into a device buffer, each chunk
+    // copied into one of two page-locked buffers and written (with the host-formatted lines spliced in) while
+    // the next one is formatted.  OGE_TEXT_CHUNK = bytes of text per chunk.
+    int write_text(ChainContext &cc, ReadBatch &b, FileFormat fmt);
     // --index: <out>.bai beside the BAM, built on the device from the records write_device compresses
     // (oge_bai_build_dev); only the one-GPU device writer provides it, every other path fails before it writes
     void setIndex(bool on) { index_ = on; }
@@ -215,6 +233,9 @@ protected:
     std::string filename_ = "stdout", program_line_;
     int level_ = 6;
     bool index_ = false;
+    FileFormat format_ = FORMAT_UNKNOWN, default_format_ = FORMAT_BAM;
+    bool detect_from_name_ = false;
+    int trim_begin_ = 0, trim_end_ = 0;
     uint64_t index_hdr_z_ = 0, index_hdr_u_ = 0;  // compressed / decompressed size of the header blocks
     std::vector<uint8_t> bai_;                    // the index image write_device built
 };

@@ -64,6 +64,12 @@ struct oge_ctx {
     bool refs_valid = false;
     std::string ref_names;
     std::vector<int32_t> ref_lens;
+    // the contig name table the last oge_text_* call uploaded (workspaces "text_names" / "text_name_off"): the
+    // next call with the same table uses it as it is
+    bool text_names_valid = false;
+    std::string text_names;
+    std::vector<uint32_t> text_name_off;
+    const void *text_names_ptr = nullptr, *text_name_off_ptr = nullptr;
     std::map<std::string, uint64_t> counters;  // per call: work counts a stage reports (oge_ctx_counter)
     bool last_scan_generic = false;  // realign scan fell back to the byte-wise kernel
     double scan_t[3] = {0, 0, 0};    // realign scan host timings: validate, upload, device + download

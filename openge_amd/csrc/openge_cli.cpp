@@ -3,20 +3,27 @@
 // dedup and localrealign, with the reference's option names and defaults.  Each command builds the
 // same module chain the reference builds (commands/command_mergesort.cpp:68-117,
 // command_dedup.cpp:48-69, command_localrealign.cpp:37-75) out of the modules in modules.h.
+// `view` is FileReader -> Filter -> FileWriter (commands/command_view.cpp:44-100), SAM to stdout by default.
 // `index`, `stats`, `count` and `coverage` are one whole-file device call each (index_bam_file,
 // stats_bam_file, count_bam_file, coverage_bam_file in modules.cpp; commands/command_stats.cpp,
 // command_count.cpp, command_coverage.cpp for the last three).
 //
-// Deliberate differences: dedup defaults to `-v --nosplit` semantics (Q1, Q3).
+// Deliberate differences: view -B/-E cuts QUAL to the window of SEQ; the reference cuts the
+// qualities of the already shortened read a second time (algorithms/filter.cpp:188-189), which leaves fewer
+// qualities than bases, bytes from behind the qualities in reads without tags, and an abort on short reads. dedup defaults to `-v --nosplit` semantics (Q1, Q3).
 // --compat-nonverbose-dedup reproduces the non-verbose index bug; --split-chains K reproduces K
 // split-by-chromosome chains, and --compat-split the reference's own rule for them (without
 // --nosplit/--nothreads: K = min(12, threads / 2), command_dedup.cpp:46-48).  Sort by name (-b)
 // gives the true name order (the reference merges name-sorted temp runs by position,
 // util/read_stream_reader.h:94-97, so its output is name-sorted only within one run of -n reads).
-// SAM/FASTQ output is not provided and fails loudly.
+// -F sam|fastq|bam: SAM text from view, mergesort, sort and dedup, FASTQ text from view to stdout, both
+// formatted on the GPU (FileWriter::write_text).  FASTQ files (the reference's _1.fastq / _2.fastq / .fastq
+// split), text output with --gpus or --index, the RAWBAM and CRAM formats and -F on localrealign fail loudly
+// before anything is read.
 #include <sys/resource.h>
 #include <sys/time.h>
 
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -47,6 +54,8 @@ const Opt kMergesort[] = {{"o", "out", true}, {"r", "region", true},  {"q", "map
                           {"b", "byname", false}, {"n", "n", true}, {"C", "compresstempfiles", false},
                           {"M", "markduplicates", false}, {"R", "removeduplicates", false}, {"", "index", false}};
 const Opt kDedup[] = {{"o", "out", true}, {"r", "remove", false}, {"", "index", false}};
+const Opt kView[] = {{"o", "out", true}, {"n", "count", true}, {"q", "mapq", true}, {"l", "length", true},
+                     {"B", "trimbegin", true}, {"E", "trimend", true}, {"r", "region", true}};
 const Opt kIndex[] = {{"o", "out", true}};
 const Opt kStats[] = {{"I", "inserts", false}, {"L", "lengths", false}};
 const Opt kCoverage[] = {{"o", "out", true}, {"b", "binsize", true}, {"", "omituncoveredbases", false},
@@ -110,9 +119,16 @@ bool parse(int argc, const char **argv, const std::vector<Opt> &opts, Parsed &p)
 }
 
 void usage_top() {
-    fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, index, stats, count, coverage,\n"
+    fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, view, index, stats, count, coverage,\n"
                     "          version\n"
-                    "\n    openge index in.bam [-o out.bai]    BAM index of a coordinate-sorted file (default in.bam.bai)\n"
+                    "\n    openge view [-o out] [-n N] [-q MAPQ] [-l LEN] [-r REGION] [-B N] [-E N] in.bam\n"
+                    "                                        the reads that pass the filters (-l: 64, 64-72, -64 or +64), as SAM\n"
+                    "                                        on stdout, else in the format of -F or of the output name's suffix;\n"
+                    "                                        -B / -E trim bases from the read ends, FASTQ only\n"
+                    "    -F sam | fastq | bam                output format of view, mergesort, sort and dedup (SAM and FASTQ text are\n"
+                    "                                        formatted on the GPU; FASTQ only from view to stdout; not with --gpus\n"
+                    "                                        or --index)\n"
+                    "    openge index in.bam [-o out.bai]    BAM index of a coordinate-sorted file (default in.bam.bai)\n"
                     "    mergesort / sort / dedup --index    also write <out>.bai (one GPU, file output, coordinate order)\n"
                     "    openge stats [-I] [-L] in.bam       flag counts, Sorted: Yes/No, insert sizes (-I), read lengths (-L)\n"
                     "    openge count in.bam                 the number of reads\n"
@@ -146,6 +162,7 @@ int main(int argc, const char **argv) {
     if (cmd == "mergesort") opts.insert(opts.end(), std::begin(kMergesort), std::end(kMergesort));
     else if (cmd == "dedup") opts.insert(opts.end(), std::begin(kDedup), std::end(kDedup));
     else if (cmd == "localrealign") opts.insert(opts.end(), std::begin(kRealign), std::end(kRealign));
+    else if (cmd == "view") opts.insert(opts.end(), std::begin(kView), std::end(kView));
     else if (cmd == "index") opts.insert(opts.end(), std::begin(kIndex), std::end(kIndex));
     else if (cmd == "stats") opts.insert(opts.end(), std::begin(kStats), std::end(kStats));
     else if (cmd == "count") ;  // no options of its own (commands/command_count.cpp)
@@ -186,6 +203,51 @@ int main(int argc, const char **argv) {
             return -1;
         }
         setenv("OGE_DEFLATE_SEARCH", s.c_str(), 1);
+    }
+    // the output format (file_writer.cpp:45-67, command_view.cpp:64-95): -F, then for view the output name's suffix,
+    // then SAM when view writes to stdout, else BAM; what is not provided fails before anything is read
+    const std::string out_name = p.get("out", "stdout");
+    const bool out_stdout = out_name == "stdout" || out_name == "-";
+    FileFormat fmt = FORMAT_BAM;
+    const bool chain_cmd = cmd == "view" || cmd == "mergesort" || cmd == "dedup" || cmd == "localrealign";
+    if (chain_cmd) {
+        if (p.count("format")) {
+            FileWriter probe;
+            if (probe.setFormat(p.get("format", "bam"))) return -1;
+            fmt = probe.getFileFormat();
+        } else if (cmd == "view") {
+            fmt = detect_file_format(out_name);
+            if (fmt == FORMAT_UNKNOWN) fmt = FORMAT_BAM;
+        }
+        if (cmd == "view" && (p.count("trimbegin") || p.count("trimend")) && fmt != FORMAT_FASTQ) {  // command_view.cpp:89-92
+            fprintf(stderr, "Trimming reads is only supported for the FASTQ format at this time. Aborting.\n");
+            return -1;
+        }
+        if (cmd == "view" && !p.count("format") && detect_file_format(out_name) == FORMAT_UNKNOWN && out_stdout) fmt = FORMAT_SAM;
+        if (fmt == FORMAT_RAWBAM || fmt == FORMAT_CRAM) {  // file_writer.cpp:192-195
+            fprintf(stderr, "Unsupported output file format selected. Aborting.\n");
+            return -1;
+        }
+        const bool text = fmt == FORMAT_SAM || fmt == FORMAT_FASTQ;
+        const char *why = !text                                  ? nullptr
+                          : cmd == "localrealign"                ? "localrealign (BAM only)"
+                          : cc.gpus > 1                          ? "--gpus"
+                          : p.count("index")                     ? "--index"
+                          : fmt == FORMAT_FASTQ && cmd != "view" ? "this command (only view writes FASTQ)"
+                          : fmt == FORMAT_FASTQ && !out_stdout   ? "an output file (only -o stdout: the _1.fastq / _2.fastq / .fastq split is not provided)"
+                                                                 : nullptr;
+        if (why) {
+            fprintf(stderr, "openge: %s output is not provided with %s\n", fmt == FORMAT_SAM ? "SAM" : "FASTQ", why);
+            return -1;
+        }
+        if (cmd == "view" && cc.gpus > 1) {
+            fprintf(stderr, "openge view: --gpus is not provided\n");
+            return -1;
+        }
+        if (cmd == "view" && (atoi(p.get("trimbegin", "0").c_str()) < 0 || atoi(p.get("trimend", "0").c_str()) < 0)) {
+            fprintf(stderr, "openge view: -B / -E must not be negative\n");
+            return -1;
+        }
     }
     if (p.count("index")) {  // what the index is not provided with fails before anything is read or written
         const char *why = p.get("out", "stdout") == "stdout" || p.get("out", "stdout") == "-" ? "output to stdout"
@@ -258,7 +320,20 @@ int main(int argc, const char **argv) {
     if (p.count("format") && writer.setFormat(p.get("format", "bam"))) return -1;
 
     int ret = 0;
-    if (cmd == "mergesort") {
+    if (cmd == "view") {  // command_view.cpp:44-100
+        Filter filter;
+        if (p.count("count")) filter.setCountLimit((int)std::min<long long>(INT32_MAX, atoll(p.get("count", "0").c_str())));
+        if (p.count("mapq")) filter.setQualityLimit(atoi(p.get("mapq", "0").c_str()));
+        if (p.count("length")) filter.setReadLengths(p.get("length", ""));
+        if (p.count("trimbegin")) filter.setTrimBeginLength(atoi(p.get("trimbegin", "0").c_str()));
+        if (p.count("trimend")) filter.setTrimEndLength(atoi(p.get("trimend", "0").c_str()));
+        if (p.count("region")) filter.setRegion(p.get("region", ""));
+        writer.setTrim(atoi(p.get("trimbegin", "0").c_str()), atoi(p.get("trimend", "0").c_str()));
+        writer.setDefaultFormat(out_stdout ? FORMAT_SAM : FORMAT_BAM);
+        reader.addSink(&filter);
+        filter.addSink(&writer);
+        ret = writer.runChain(cc);
+    } else if (cmd == "mergesort") {
         bool dedup = p.count("markduplicates") || p.count("removeduplicates");
         Filter filter;
         ReadSorter sorter;

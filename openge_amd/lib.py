@@ -60,6 +60,23 @@ class BamStats(C.Structure):
 
 
 STATS_INSERTS, STATS_LENGTHS = 1, 2
+TEXT_SAM, TEXT_FASTQ = 0, 1
+
+
+class TextOpts(C.Structure):
+    """oge_text_opts: the text mode, the FASTQ trim window and the contig names of the header."""
+    _fields_ = [("mode", C.c_int32), ("trim_begin", C.c_int32), ("trim_end", C.c_int32), ("n_ref", C.c_int32),
+                ("ref_names", C.c_char_p), ("ref_name_off", C.c_void_p)]
+
+
+def text_opts(names: list[str], mode: int = TEXT_SAM, trim: tuple[int, int] = (0, 0)) -> tuple[TextOpts, tuple]:
+    """(oge_text_opts, the buffers it points into: keep them alive while it is in use)"""
+    enc = [nm.encode() for nm in names]
+    off = np.zeros(len(enc) + 1, np.uint32)
+    off[1:] = np.cumsum([len(e) for e in enc], dtype=np.uint64) if enc else []
+    blob = b"".join(enc)
+    o = TextOpts(mode, trim[0], trim[1], len(enc), blob, _ptr(off))
+    return o, (blob, off)
 
 
 class MergesortOpts(C.Structure):
@@ -300,6 +317,10 @@ def lib() -> C.CDLL:
         "oge_bam_coverage_dev": (C.c_int, [vp, vp, u64, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]),
         "oge_bam_count_dev": (C.c_int, [vp, vp, u64, C.POINTER(u64)]),
         "oge_ctx_last_refs": (C.c_int, [vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp)]),
+        "oge_text_size_dev": (C.c_int, [vp, vp, vp, u64, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]),
+        "oge_text_emit_dev": (C.c_int, [vp, vp, vp, vp, u64, u64, vp, vp, u64]),
+        "oge_text_host_line": (C.c_int, [vp, u64, vp, vp, u64, C.POINTER(u64)]),
+        "oge_text_format": (C.c_int, [vp, vp, u64, vp, u64, vp, vp, u64, C.POINTER(u64)]),
         "oge_mergesort_opts_init": (None, [vp]),
         "oge_mergesort_bgzf_dev": (C.c_int, [vp, vp, u64, vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64),
                                              C.POINTER(u64)]),
@@ -676,6 +697,38 @@ class Context:
         if lengths:
             out["lengths"] = (ln[:st.n_lengths], ct[:st.n_lengths])
         return out
+
+    # ---- SAM / FASTQ text (csrc/sam.hip)
+    def text_size_dev(self, d_recs, d_off, n: int, opts: TextOpts, d_text_off, d_host_mark) -> tuple[int, int]:
+        """oge_text_size_dev: fills d_text_off (n + 1 u64) and d_host_mark (n u8) -> (device text bytes, host lines)."""
+        total, n_host = C.c_uint64(), C.c_uint64()
+        check(lib().oge_text_size_dev(self.h, d_recs, d_off, n, C.byref(opts), d_text_off, d_host_mark, C.byref(total), C.byref(n_host)), self.h)
+        return total.value, n_host.value
+
+    def text_emit_dev(self, d_recs, d_off, d_text_off, first: int, count: int, opts: TextOpts, d_out, cap: int) -> None:
+        """oge_text_emit_dev: the text of records [first, first + count) at d_out."""
+        check(lib().oge_text_emit_dev(self.h, d_recs, d_off, d_text_off, first, count, C.byref(opts), d_out, cap), self.h)
+
+    def text_format(self, recs: np.ndarray, offs: np.ndarray, n: int, opts: TextOpts) -> bytes:
+        """oge_text_format: the whole text of host records, the host-formatted lines spliced in."""
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nb = C.c_uint64()
+        args = (self.h, _ptr(recs), max(recs.nbytes - 16, 0), _ptr(offs), n, C.byref(opts))
+        rc = lib().oge_text_format(*args, None, 0, C.byref(nb))
+        if not (rc == -3 and nb.value):  # OGE_ERR_LIMIT with the size: the sizing call
+            check(rc, self.h)
+            return b""
+        out = np.empty(nb.value, np.uint8)
+        check(lib().oge_text_format(*args, _ptr(out), out.nbytes, C.byref(nb)), self.h)
+        return out[:nb.value].tobytes()
+
+    @staticmethod
+    def text_host_line(rec: bytes, opts: TextOpts) -> bytes:
+        """oge_text_host_line: one record's text formatted on the host."""
+        nb = C.c_uint64()
+        buf = C.create_string_buffer(16 + 12 * len(rec) + 256 * 2)
+        check(lib().oge_text_host_line(rec, len(rec), C.byref(opts), buf, len(buf), C.byref(nb)))
+        return buf.raw[:nb.value]
 
     @staticmethod
     def coverage_layout(ref_len, binsize: int) -> np.ndarray:
