@@ -69,7 +69,10 @@ constexpr uint64_t kChunkLanes = OGE_INFL_CHUNK;  // blocks per lane per chunk, 
 constexpr int LB = OGE_INFL_LB;  // literals per batch (see the ST_SYM path; 20M reads, LB 3 / 4 / 5 / 6:
                                  // 48.1 / 45.1 / 43.5 / 43.2 ms)
 #ifndef OGE_INFL_ITER  // iteration shape (build knob): 0 batch + symbol + batch, 1 symbol + 2 batches, 2 batch +
-#define OGE_INFL_ITER 0  // symbol + 2 batches; 20M reads (LB 6): 43.8 / 43.6 / 45.6 ms
+#define OGE_INFL_ITER 0  // symbol + 2 batches; 20M reads (LB 6): 43.8 / 43.6 / 45.6 ms (r06; 2 no longer builds: it has
+#endif                   // five refill sites, the input queue of r07 feeds four an iteration)
+#ifndef OGE_INFL_RELOAD  // where an iteration's reload point sits (build knob): 0 at its top, 1 after the first
+#define OGE_INFL_RELOAD 1  // batch's lookups, before its store
 #endif
 #ifndef OGE_INFL_INNER
 #define OGE_INFL_INNER 16
@@ -129,6 +132,8 @@ template <int N, class F>
 __device__ __forceinline__ void sfor(F &&f) {
     sfor_(f, std::make_integer_sequence<int, N>{});
 }
+template <int K>
+using Site = std::integral_constant<int, K>;  // a refill site of phase 1 (see refill)
 template <int N>
 __device__ __forceinline__ uint32_t pick(const uint32_t (&a)[N], uint32_t i) {  // a[i], i < N, in VGPRs
     uint32_t v = a[0];
@@ -160,7 +165,8 @@ __device__ __forceinline__ void tset(Slow &T, uint32_t v) {
 template <int NR, int TB, bool LIT>
 __device__ bool wbuild(P1Lds &S, uint32_t j, OGE_G uint8_t *list, OGE_G uint8_t *xl, const uint32_t (&len)[NR], uint32_t n,
                        uint32_t *lim, uint32_t *pk, uint32_t *nlong) {
-    const uint32_t lane = threadIdx.x;
+    uint32_t lane = threadIdx.x;
+    __asm__ volatile("" : "+v"(lane));  // see k_infl_huff's wave-wide phases
     const uint64_t lt = (1ull << lane) - 1;
     if (lane < 16) S.cnt[lane] = S.lo[lane] = 0;
     __builtin_amdgcn_wave_barrier();
@@ -558,56 +564,110 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
                                                       const uint8_t *__restrict__ prep, const uint32_t *__restrict__ pmeta) {
     static_assert(LB + 1 < 8, "a batch and the pending literal: fewer bytes than the 8-byte register (put_n shifts < 64)");
     static_assert(sizeof(P1Lds) <= 13312, "12 waves per CU");
+    static_assert(OGE_INFL_ITER < 2, "five refill sites in an iteration: the input queue feeds four between two reload points");
     __shared__ P1Lds S;
     const uint32_t lane = threadIdx.x;
-    auto scr = [&]() { return (OGE_G uint8_t *)(scratch + ((uint64_t)blockIdx.x * 64 + threadIdx.x) * kScr); };  // lens / list
+    auto scr = [&]() {  // lens / list.  Recomputed at each (rare) use: hoisted, the address is two VGPRs held through the decode loop
+        uint32_t l = threadIdx.x;
+        __asm__ volatile("" : "+v"(l));
+        return (OGE_G uint8_t *)(scratch + ((uint64_t)blockIdx.x * 64 + l) * kScr);
+    };
     const uintptr_t zend = (uintptr_t)z + zbytes;
     const uintptr_t zlast = (zend - 1) & ~(uintptr_t)15;  // the stream's last 16-byte chunk
 
-    // input: 64-bit bit buffer + two 16-byte chunks (q being consumed, p loaded ahead)
+    // input: a 64-bit bit buffer fed from a queue of three 16-byte chunks, q <- p <- r.
+    //   q: the chunk being consumed (q.x next, qn dwords left); p: the chunk after it (pn = 4: present, 0: taken);
+    //   r: the chunk after p, loaded from memory.  cp: the address after r's chunk.  qp = qn | pn << 4.
+    // refill() tops the bit buffer up from q, and q from p, in registers only: no load and no wait for one sits
+    // in a lane-divergent branch of an iteration.  Memory is read at ONE point per decode iteration, reload(),
+    // which the whole wave executes: a lane whose p is empty takes r -- the chunk it loaded at an EARLIER
+    // iteration's reload point -- and loads the next chunk into r.  The wave's single wait for its loads
+    // therefore has a whole iteration of its own work, and the other waves', behind it.
+    // (r06: the load sat in refill()'s hand-over branch.  A lane reloads every fourth iteration or so, but
+    // s_waitcnt counts for the wave: some lane of the 64 reloaded at nearly every refill site, so the wave
+    // waited vmcnt(0) -- for another lane's load issued a quarter of an iteration earlier and for every
+    // output store in flight -- about four times an iteration.  100M reads, alternated processes: infl_huff
+    // 98.3-101.0 -> 76.7-80.2 ms; with every lane loading at the reload point, the idle ones their r's chunk
+    // again through a select on the address, 100.0-104.5 ms: four times the vector-memory instructions' lane
+    // work, and the stores queue behind it.  profiles/r07a_infl_reload_split.txt.)
+    // Invariant: after reload() q and p hold >= 4 dwords (p is full), and until the next reload() a lane
+    // takes at most 4: an ST_SYM iteration has four refill sites, and every other state consumes <= 74 bits
+    // between two reload points (a take needs cnt <= 32 and leaves cnt <= 64, so t takes need
+    // 32 t <= 64 + bits consumed).  No lane ever sits an iteration out; the guard in refill() turns a broken
+    // invariant into E_BITS.
     uint64_t buf = 0;
     uint32_t under = 0;  // a skip past the buffered bits happened in this block (the guard)
-    // q: the chunk being consumed (q.x next), p: the next chunk, loaded ahead.  Both are 4-register tuples:
-    // a load lands in p's own registers (four scalar u32s made the compiler load into a temporary tuple
-    // and copy it out at once -- a wait for the load right where it was issued)
+    // 4-register tuples: a load lands in r's own registers (four scalar u32s made the compiler load into a
+    // temporary tuple and copy it out at once -- a wait for the load right where it was issued)
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 q = {0, 0, 0, 0}, p = {0, 0, 0, 0};
-    uint32_t cnt = 0, qn = 0;
-    uintptr_t cp = 0;
+    u32x4 q = {0, 0, 0, 0}, p = {0, 0, 0, 0}, r = {0, 0, 0, 0};
     // A 16-byte aligned chunk holding at least one stream byte never leaves its page; past the end the
     // last chunk is loaded again (only a corrupt stream reads those bits, and it fails E_PAST / E_BITS).
-    // No branch around the load: a value merged after a branch is waited for on the spot, and the
-    // prefetch one chunk ahead would wait for its HBM round trip -- and, vmcnt counting stores too, for
-    // every output store in flight -- at every fourth refill.
+    uint32_t cnt = 0, qp = 4 << 4;  // p "full": a lane without a block loads nothing
+    uintptr_t cp = zlast + 16;
     auto load16 = [&](uintptr_t a) { return *(const OGE_G u32x4 *)(a < zend ? a : zlast); };
-#if OGE_EXP == 2  // timing experiment: cycles spent taking the prefetched chunk (its wait) vs the decode loop
-    uint64_t x_wait = 0, x_loop = 0, x_steps = 0;
-#endif
 #if OGE_EXP == 3  // timing experiment: a wave's cycles in the table builds / block taking / decode loop, and
                   // how many of its decode iterations run each state's path (some lane in that state)
     uint64_t y_bld = 0, y_nxt = 0, y_loop = 0, y_clc = 0, y_oc = 0;
     uint32_t y_it = 0, y_cl = 0, y_hdr = 0, y_sto = 0, y_sym = 0, y_nbcl = 0, y_nbld = 0, y_blk = 0;
 #endif
-    auto refill = [&]() {
+#if OGE_EXP == 8  // timing experiment: a wave's cycles in the ST_SYM path's reload hand-overs (the wait for the
+                  // chunk loaded ahead), by refill site, and in its output-store sites.  No registers to spare:
+                  // the first active lane adds a site's cycles to S.cnt / its visits to S.lo (free between the
+                  // builds), and lane k collects site k's after every kInner steps
+    uint32_t x_cyc = 0, x_vis = 0;
+    uint64_t x_loop = 0, x_steps = 0;
+    if (lane < 16) S.cnt[lane] = S.lo[lane] = 0;
+    auto x_now = [&]() {
+        unsigned long long t;
+        __builtin_amdgcn_sched_barrier(0);
+        __asm__ volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+        __builtin_amdgcn_sched_barrier(0);
+        return (uint64_t)t;
+    };
+    auto x_add = [&](int k, uint64_t c0) {
+        const uint32_t d = (uint32_t)(x_now() - c0);
+        if (lane == (uint32_t)__builtin_ctzll(__ballot(true))) atomicAdd(&S.cnt[k], d), atomicAdd(&S.lo[k], 1u);
+    };
+#endif
+    auto refill = [&](auto site) {  // site: 0 / 3 the literal batches, 1 the main symbol, 2 the distance, 4 other states
         if (cnt <= 32) {
+            if ((qp & 15) == 0) {
+#if OGE_EXP == 8
+                const uint64_t c0 = x_now();
+#endif
+                q = p, qp >>= 4;       // qn = pn, pn = 0
+                under |= qp == 0;  // never: see the invariant
+#if OGE_EXP == 8
+                if (qp == 0) atomicAdd(&S.cnt[7], 1u);  // lanes that ran dry (would have had to sit out)
+                __asm__ volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w)::"memory");
+                x_add(decltype(site)::value, c0);
+#endif
+            }
             buf |= (uint64_t)q.x << cnt;
             cnt += 32;
             q.x = q.y, q.y = q.z, q.z = q.w;
-            if (--qn == 0) {
-#if OGE_EXP == 2
-                const uint64_t c0 = __builtin_readcyclecounter();
-                q = p, qn = 4;
-                __asm__ volatile("" ::"v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w));
-                x_wait += __builtin_readcyclecounter() - c0;
-#else
-                q = p, qn = 4;
-                // q takes p's values before the next load is issued, so the load can land in p's registers
-                __asm__ volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w)::"memory");
-#endif
-                p = load16(cp);
-                cp += 16;
-            }
+            qp = max(qp, 1u) - 1;
         }
+    };
+    // the iteration's one reload point (see above); all 64 lanes, whatever their state
+    auto reload = [&]() {
+#if OGE_EXP == 8
+        const uint64_t c0 = x_now();
+#endif
+        const bool adv = qp < 16;  // pn == 0
+        p.x = adv ? r.x : p.x, p.y = adv ? r.y : p.y, p.z = adv ? r.z : p.z, p.w = adv ? r.w : p.w;
+        qp = (qp & 15) | (4 << 4);
+        // p takes r's values (the wave's wait for last iteration's loads is HERE) before the next load is
+        // issued, so the load can land in r's registers
+        __asm__ volatile("" : "+v"(p.x), "+v"(p.y), "+v"(p.z), "+v"(p.w)::"memory");
+        if (adv) {  // lanes that took r: the load lands in r's registers under their exec mask, no wait follows
+            r = load16(cp);
+            cp += 16;
+        }
+#if OGE_EXP == 8
+        x_add(6, c0);
+#endif
     };
     auto skip = [&](uint32_t k) {
         under |= k > cnt;
@@ -619,18 +679,20 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
         skip(k);
         return v;
     };
-    auto bitpos = [&]() -> uint64_t { return (uint64_t)(cp - 16 - 4 * qn) * 8 - cnt; };
+    // bytes fetched and not yet in buf: r's 16, p's 4 * pn, q's 4 * qn
+    auto bitpos = [&]() -> uint64_t { return (uint64_t)(cp - 16 - 4 * ((qp >> 4) + (qp & 15))) * 8 - cnt; };
     auto seek = [&](uintptr_t a) {  // start reading at byte address a
         const uintptr_t al = a & ~(uintptr_t)15;
         q = load16(al);
         p = load16(al + 16);
-        cp = al + 32;
-        qn = 4;
-        for (uint32_t k = 0; k < (uint32_t)((a - al) >> 2); ++k) q.x = q.y, q.y = q.z, q.z = q.w, --qn;
+        r = load16(al + 32);
+        cp = al + 48;
+        qp = 4 | (4 << 4);
+        for (uint32_t k = 0; k < (uint32_t)((a - al) >> 2); ++k) q.x = q.y, q.y = q.z, q.z = q.w, --qp;
         buf = 0;
         cnt = 0;
-        refill();
-        refill();
+        refill(Site<4>{});
+        refill(Site<4>{});
         skip((uint32_t)(a & 3) * 8);
     };
 
@@ -641,6 +703,9 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
     uint64_t acc = 0;
     auto store_chunk = [&](uint32_t c, uint64_t v) {  // chunk c (8 bytes at ob8 + 8c) = v
         OGE_G uint64_t *A = (OGE_G uint64_t *)ob8 + c;
+#if OGE_EXP == 8
+        const uint64_t c0 = x_now();
+#endif
         if ((c == 0 && al) || (c == clast && ((al + osz) & 7))) {  // shared with a neighbouring block
             for (uint32_t k = 0; k < 8; ++k) {
                 const uint32_t q = 8 * c + k;
@@ -649,6 +714,9 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
         } else {
             *A = v;
         }
+#if OGE_EXP == 8
+        x_add(5, c0);
+#endif
     };
     auto put = [&](uint32_t v) {  // one byte at pos
         acc = (acc >> 8) | ((uint64_t)(v & 0xff) << 56);
@@ -679,8 +747,9 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
     // into two words instead of a variable 64-bit shift and two selects per literal, the output-room test a
     // compare with the constant k, and the pending byte joined once per batch (100M reads: infl_huff 105.5 ->
     // 98.0 ms)
-    auto lit_batch = [&](uint32_t pb, uint32_t np) {
-        refill();
+    // lit_decode: the batch's bytes (the first in the low byte) and their number; lit_batch puts them too
+    auto lit_decode = [&](uint32_t np, auto site, uint64_t &batch, uint32_t &nb) {
+        refill(site);
         const int32_t room = (int32_t)(osz - pos - np);  // >= 0: pos + np <= osz here
         uint32_t lo = 0, hi = 0, n = 0;
         bool go = true;
@@ -698,20 +767,34 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
             else hi |= b << (8 * (k - 4));
             n += go;
         }
-        const uint64_t batch = (uint64_t)lo | ((uint64_t)hi << 32);
+        batch = (uint64_t)lo | ((uint64_t)hi << 32);
+        nb = n;
+    };
+    auto lit_batch = [&](uint32_t pb, uint32_t np, auto site) {
+        uint64_t batch;
+        uint32_t n;
+        lit_decode(np, site, batch, n);
         put_n(np ? (uint64_t)pb | (batch << 8) : batch, n + np);
     };
     // hole and deferred-literal bitmaps of the block (1024 word pairs per block of the chunk)
     uint64_t bm = 0, lm = 0;
-    uint32_t bw = 0, bi = 0;  // word, block index in the chunk
+    uint32_t bw = 0;  // word
+    uint32_t b = 0;   // block index (a chunk of a launch holds < 2^32 blocks)
+    auto bi = [&]() { return b - (uint32_t)b0; };  // its index in the chunk
     auto word = [&](uint32_t p) {
         const uint32_t w = p >> 6;
         if (w != bw) {
             if (bm | lm) {
+#if OGE_EXP == 8
+                const uint64_t c0 = x_now();
+#endif
                 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
                 u64x2 v;
                 v.x = bm, v.y = lm;
-                *(OGE_G u64x2 *)(bitmap + (uint64_t)bi * kBmStride + 2 * bw) = v;
+                *(OGE_G u64x2 *)(bitmap + (uint64_t)bi() * kBmStride + 2 * bw) = v;
+#if OGE_EXP == 8
+                x_add(5, c0);
+#endif
             }
             bm = lm = 0;
             bw = w;
@@ -728,7 +811,6 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
     // hl: hlit | hdist << 16; aux: the code-length walk (ci | prev << 16 | l256 << 24) or a stored block's
     // bytes left; flg: the block header's BFINAL (1) and fixed-codes (2) bits
     uint32_t st = ST_NEXT, hl = 0, aux = 0, flg = 0;
-    uint32_t b = 0;  // block index (a chunk of a launch holds < 2^32 blocks)
 
     // a failing block: the lane stops decoding it at once, the error is reported (atomics on err) in the
     // next wave-wide phase, before the lane takes another block -- no atomics inlined into the decode
@@ -758,9 +840,15 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
         y_nbcl += (uint32_t)__popcll(__ballot(st == ST_BCL));
         y_nbld += (uint32_t)__popcll(__ballot(st == ST_BLD));
 #endif
+        // The wave-wide phases below use a lane number the compiler cannot see through: whatever they derive
+        // from it (LDS addresses, the fixed code's lengths, loop bounds) is computed here, where it is used --
+        // hoisted out of the block loop it was a dozen VGPRs held through the decode loop, and spills
+        uint32_t lw = lane;
+        __asm__ volatile("" : "+v"(lw));
         uint64_t need = __ballot(st == ST_BCL || st == ST_BLD);
         if (need) __threadfence_block();  // lanes' code-length stores before the wave reads them
         while (need) {
+            const uint32_t lane = lw;
             const uint32_t j = (uint32_t)__builtin_ctzll(need);
             need &= need - 1;
             OGE_G uint8_t *sj = (OGE_G uint8_t *)(scratch + ((uint64_t)blockIdx.x * 64 + j) * kScr);
@@ -813,7 +901,7 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
                 dl[0] = lane < hd ? (fx ? 5u : (uint32_t)sj[S_LENS + hl + lane]) : 0u;
                 // the long-code list: the lane's scratch, and the block's translation area while it has a
                 // free table slot (else the table's long literals are looked up in the chain, as r03 did)
-                OGE_G uint8_t *xj = (OGE_G uint8_t *)(xtab + (uint64_t)__builtin_amdgcn_readlane(bi, j) * kXTab);
+                OGE_G uint8_t *xj = (OGE_G uint8_t *)(xtab + (uint64_t)__builtin_amdgcn_readlane(bi(), j) * kXTab);
                 uint32_t lim, pk, nlong;
                 bool ok = wbuild<5, TL, true>(S, j, sj + S_LS, nt < kNT ? xj + nt * kXList : nullptr, ll, hl, &lim, &pk, &nlong);
                 const uint32_t dfr = ok && nt < kNT && nlong <= 256;
@@ -875,13 +963,12 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
                 clast = (al + osz + 7) / 8 - 1;
                 pos = 0;
                 acc = 0;
-                bi = (uint32_t)(b - b0);
                 bm = lm = 0;
                 bw = 0;
                 // the pre-pass's verdict: prepared (tables ready, the first symbol's bit offset) or not
-                const uint32_t pm = pmeta ? pmeta[bi] : 0u;
+                const uint32_t pm = pmeta ? pmeta[bi()] : 0u;
                 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                *(OGE_G u32x4 *)(xtab + (uint64_t)bi * kXTab + kXStart) =
+                *(OGE_G u32x4 *)(xtab + (uint64_t)bi() * kXTab + kXStart) =
                     u32x4{(pm >> 29) & 1 ? 0u : 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
                 tabs = 0;
                 const uint32_t u = pm & 0xffffff;
@@ -900,9 +987,10 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
         // registers by the whole wave, one 8-byte load per lane; the next lane's record is loaded while
         // this one is written
         if (uint64_t ld = __ballot(st == ST_LOAD)) {
+            const uint32_t lane = lw;
             typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
             auto rec = [&](uint32_t j) {
-                const uint32_t bj = __builtin_amdgcn_readlane(bi, j);
+                const uint32_t bj = __builtin_amdgcn_readlane(bi(), j);
                 const OGE_G u32x2 *R = (const OGE_G u32x2 *)(prep + (uint64_t)bj * kPrep);
                 return lane < kPrep / 8 ? R[lane] : u32x2{0u, 0u};
             };
@@ -947,19 +1035,23 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
                        blockIdx.x, (unsigned long long)y_bld, (unsigned long long)y_nxt, (unsigned long long)y_loop, y_it, y_cl,
                        y_hdr, y_sto, y_sym, y_blk, y_nbcl, y_nbld, (unsigned long long)y_clc, (unsigned long long)y_oc);
 #endif
-#if OGE_EXP == 2
-            uint64_t w = x_wait;
+#if OGE_EXP == 8
+            {
+                uint32_t c[8], n[8];
 #pragma unroll
-            for (int d = 1; d < 64; d <<= 1) w = max(w, (uint64_t)__shfl_xor((unsigned long long)w, d, 64));
-            if (lane == 0 && blockIdx.x < 8)
-                printf("infl-exp wave %u: loop cycles %llu, steps %llu, max lane wait cycles %llu\n", blockIdx.x,
-                       (unsigned long long)x_loop, (unsigned long long)x_steps, (unsigned long long)w);
+                for (int i = 0; i < 8; ++i) c[i] = (uint32_t)__shfl(x_cyc, i, 64), n[i] = (uint32_t)__shfl(x_vis, i, 64);
+                if (lane == 0 && blockIdx.x < 16)
+                    printf("infl-exp8 wave %u: loop cycles %llu iters %llu | hand-over cycles/visits batch1 %u/%u main %u/%u dist %u/%u "
+                           "batch2 %u/%u other %u/%u | store sites %u/%u | reload point %u/%u | lanes run dry %u\n", blockIdx.x,
+                           (unsigned long long)x_loop, (unsigned long long)x_steps, c[0], n[0], c[1], n[1], c[2], n[2], c[3], n[3], c[4],
+                           n[4], c[5], n[5], c[6], n[6], c[7]);
+            }
 #endif
             break;
         }
 
         // ---- kInner decode steps; a lane that reaches a wave-wide state (build, next block) idles
-#if OGE_EXP == 2
+#if OGE_EXP == 8
         const uint64_t l0 = __builtin_readcyclecounter();
         x_steps += kInner;
 #endif
@@ -976,15 +1068,27 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
             y_sto += __ballot(st == ST_STORED) != 0;
             y_sym += __ballot(st == ST_SYM) != 0;
 #endif
+            // the reload point (see the input queue): the wait for the chunks loaded one iteration ago, and
+            // the next loads.  After the first batch's lookups and before its store, so that the youngest
+            // output store the wait also covers (gfx9 counts stores in vmcnt) -- the second batch's, at the
+            // end of the previous iteration -- is a batch's lookup chain old
+#if OGE_INFL_RELOAD == 1 && OGE_INFL_ITER != 1
+            uint64_t b1 = 0;
+            uint32_t n1 = 0;
+            if (st == ST_SYM) lit_decode(0, Site<0>{}, b1, n1);
+#endif
+            reload();
             if (st == ST_SYM) {
                 // an iteration: up to LB direct literals, one symbol of any kind, up to LB direct literals.
                 // A wave runs the union of its lanes' paths, so a lane should make as much progress per
                 // iteration as the union costs: a match and the literals around it in one pass (C2 blocks:
                 // 11.5k iterations per BGZF block instead of 19.8k one-symbol steps; tools/ana policy)
-#if OGE_INFL_ITER != 1
-                lit_batch(0, 0);
+#if OGE_INFL_RELOAD == 1 && OGE_INFL_ITER != 1
+                put_n(b1, n1);
+#elif OGE_INFL_ITER != 1
+                lit_batch(0, 0, Site<0>{});
 #endif
-                refill();
+                refill(Site<1>{});
                 uint32_t pb = 0, np = 0;  // a literal main symbol: put with the second batch
                 const uint32_t v = (uint32_t)buf;
                 const uint32_t e = S.lt[v & ((1u << TL) - 1)][lane];
@@ -1006,7 +1110,15 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
                     const uint32_t k = ((pk & 0xffff) + (c15 >> (15 - L))) & 0xffff;
                     const uint32_t litend = (pk >> 16) & 511;
                     if (k < litend) {  // a literal: its byte later (phase 2), or now from the lane's scratch
-                        sym = (tabs & 1) ? kDefer | k : (uint32_t)scr()[S_LS + min(k, 287u)];
+                        if (tabs & 1) {
+                            sym = kDefer | k;
+                        } else {
+                            // waited for here, inside the branch: merged with the other side first, the
+                            // compiler waits (vmcnt(0): the input loads, the stores) after the merge, where
+                            // every iteration with a long code passes
+                            sym = (uint32_t)scr()[S_LS + min(k, 287u)];
+                            __asm__ volatile("" : "+v"(sym));
+                        }
                     } else {  // a length code or end of block: LDS
                         sym = 256u + S.ll[min(k - litend + (pk >> 25), 31u)][lane];
                     }
@@ -1033,7 +1145,7 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
                     const uint32_t ext = c < 8 ? 0u : c < 28 ? (c - 4) >> 2 : 0u;
                     const uint32_t base = c < 8 ? c + 3 : c < 28 ? ((4 + (c & 3)) << ext) + 3 : 258u;
                     const uint32_t len = base + get(ext);
-                    refill();
+                    refill(Site<2>{});
                     const uint32_t w = (uint32_t)buf;
                     const uint32_t de = S.dt[w & ((1u << TD) - 1)][lane];
                     uint32_t ds, DL;
@@ -1078,12 +1190,12 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
                         }
                     }
                 }
-                if (st == ST_SYM) lit_batch(pb, np);  // a failed block drops its pending byte
+                if (st == ST_SYM) lit_batch(pb, np, Site<3>{});  // a failed block drops its pending byte
 #if OGE_INFL_ITER >= 1
-                if (st == ST_SYM) lit_batch(0, 0);
+                if (st == ST_SYM) lit_batch(0, 0, Site<3>{});
 #endif
             } else if (st == ST_CL) {
-                refill();
+                refill(Site<4>{});
                 const uint32_t e = ((const uint8_t *)&S.lt[0][0])[cl_at((uint32_t)buf & 127, lane)];
                 const uint32_t s = e & 31, L = e >> 5;
                 skip(L);
@@ -1112,13 +1224,13 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
                     }
                 }
             } else if (st == ST_HDR) {
-                refill();
+                refill(Site<4>{});
                 const uint32_t h = get(3);
                 flg = h & 1;
                 const uint32_t type = h >> 1;
                 if (type == 0) {
                     skip((8 - (uint32_t)(bitpos() & 7)) & 7);
-                    refill();
+                    refill(Site<4>{});
                     const uint32_t len = get(16), nlen = get(16);
                     if ((len ^ 0xffffu) != nlen) fail(E_STORED);
                     else if (pos + len > osz) fail(E_OVERRUN);
@@ -1137,7 +1249,7 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
 #pragma unroll
                         for (int i = 0; i < 19; ++i) {
                             if ((uint32_t)i < hclen) {
-                                refill();
+                                refill(Site<4>{});
                                 c |= (uint64_t)get(3) << (3 * kClOrd[i]);
                             }
                         }
@@ -1148,7 +1260,7 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
                     fail(E_TYPE);
                 }
             } else if (st == ST_STORED) {
-                refill();
+                refill(Site<4>{});
                 const uint32_t k = min(aux, 4u);
                 for (uint32_t i = 0; i < k; ++i) put(get(8));
                 aux -= k;
@@ -1165,8 +1277,14 @@ __global__ void __launch_bounds__(64, kWps) k_infl_huff(const uint8_t *__restric
             }
 #endif
         }
-#if OGE_EXP == 2
+#if OGE_EXP == 8
         x_loop += __builtin_readcyclecounter() - l0;
+#endif
+#if OGE_EXP == 8
+        if (lane < 16) {
+            x_cyc += S.cnt[lane], x_vis += S.lo[lane];
+            S.cnt[lane] = S.lo[lane] = 0;
+        }
 #endif
 #if OGE_EXP == 3
         y_loop += __builtin_readcyclecounter() - y2;
