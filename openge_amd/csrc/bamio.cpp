@@ -595,6 +595,23 @@ bool bam_parse(bytevec &&raw, BamFile &out, std::string &err, int threads) {
     return true;
 }
 
+bool pread_all(int fd, void *dst, uint64_t off, uint64_t len, uint64_t slice, int threads) {
+    std::atomic<bool> bad(false);
+    parallel_for((size_t)((len + slice - 1) / slice), threads, [&](size_t k) {
+        uint64_t o = k * slice;
+        const uint64_t e = std::min(len, o + slice);
+        while (o < e) {
+            const ssize_t r = pread(fd, (uint8_t *)dst + o, e - o, (off_t)(off + o));
+            if (r <= 0) {
+                bad = true;
+                return;
+            }
+            o += (uint64_t)r;
+        }
+    });
+    return !bad;
+}
+
 bool read_file_bytes(const std::string &path, bytevec &comp, int threads, std::string &err) {
     FILE *f = (path == "-" || path == "stdin") ? stdin : fopen(path.c_str(), "rb");
     if (!f) { err = "cannot open " + path; return false; }
@@ -604,21 +621,7 @@ bool read_file_bytes(const std::string &path, bytevec &comp, int threads, std::s
         comp.reserve(sz > 0 ? (size_t)sz : 0);
         want_huge_pages(comp.data(), comp.capacity());
         comp.resize(sz > 0 ? (size_t)sz : 0);
-        const int fd = fileno(f);
-        const size_t chunk = 64ull << 20, nch = (comp.size() + chunk - 1) / chunk;
-        std::atomic<bool> short_read(false);
-        parallel_for(nch, threads, [&](size_t c) {
-            size_t o = c * chunk, e = std::min(comp.size(), o + chunk);
-            while (o < e) {
-                ssize_t r = pread(fd, comp.data() + o, e - o, (off_t)o);
-                if (r <= 0) {
-                    short_read = true;
-                    return;
-                }
-                o += (size_t)r;
-            }
-        });
-        if (short_read) {
+        if (!pread_all(fileno(f), comp.data(), 0, comp.size(), 64ull << 20, threads)) {
             fclose(f);
             err = "short read on " + path;
             return false;

@@ -106,6 +106,9 @@ bool bam_read_file(const std::string &path, BamFile &out, int threads, std::stri
 // madvise(MADV_HUGEPAGE) over a large buffer before its first touch
 void want_huge_pages(void *p, size_t n);
 bool bam_parse(bytevec &&raw, BamFile &out, std::string &err, int threads = 1);
+// dst[0, len) from the open file's bytes [off, off + len): preads of `slice` bytes, on up to `threads` threads.
+// False when a read fails or the file ends first.
+bool pread_all(int fd, void *dst, uint64_t off, uint64_t len, uint64_t slice, int threads);
 // The whole file (parallel pread for regular files).
 bool read_file_bytes(const std::string &path, bytevec &comp, int threads, std::string &err);
 // Header text, @SQ / binary reference list of a decompressed stream prefix d[0, n) -> *rec_base.

@@ -27,6 +27,10 @@ namespace oge {
 
 bool AlgorithmModule::verbose_ = false;
 
+using TimePoint = std::chrono::steady_clock::time_point;
+static TimePoint clk() { return std::chrono::steady_clock::now(); }
+static double sec(TimePoint a, TimePoint z) { return std::chrono::duration<double>(z - a).count(); }
+
 int ChainContext::fail(const std::string &where) {
     fprintf(stderr, "openge: %s: %s\n", where.c_str(), oge_last_error(ctx));
     return -1;
@@ -41,12 +45,12 @@ static bool write_device_forced() {
 int ChainContext::to_device(ReadBatch &b) {
     if (b.dev_valid) return 0;
     const uint64_t bytes = b.offs[b.n];
-    void *r = nullptr, *o = nullptr;
-    if (oge_dev_alloc(ctx, bytes + 64, &r) || oge_dev_alloc(ctx, (b.n + 1) * 8, &o)) return fail("device allocation");
-    if (oge_memcpy(ctx, r, b.recs.data(), bytes, 1) || oge_memcpy(ctx, o, b.offs.data(), (b.n + 1) * 8, 1))
+    DevBuf r(ctx), o(ctx);
+    if (r.alloc(bytes + 64) || o.alloc((b.n + 1) * 8)) return fail("device allocation");
+    if (oge_memcpy(ctx, r.as<void>(), b.recs.data(), bytes, 1) || oge_memcpy(ctx, o.as<void>(), b.offs.data(), (b.n + 1) * 8, 1))
         return fail("host->device copy");
-    b.d_recs = (uint8_t *)r;
-    b.d_offs = (uint64_t *)o;
+    b.d_recs = (uint8_t *)r.release();
+    b.d_offs = (uint64_t *)o.release();
     b.d_bytes = bytes;
     b.dev_valid = true;
     return 0;
@@ -159,20 +163,18 @@ int run_ranks(ChainContext &cc, ReadBatch &b, bool sort, const oge_markdup_opts 
                 return;
             }
             const uint64_t lo = cut[g], m = cut[g + 1] - lo, bytes = boff[g + 1] - boff[g];
-            void *r = nullptr, *o = nullptr;
-            int rc = oge_dev_alloc(c, bytes + 64, &r);
-            if (!rc) rc = oge_dev_alloc(c, (m + 1) * 8, &o);
-            if (!rc && bytes) rc = oge_memcpy(c, r, b.d_recs + boff[g], bytes, 4);
-            if (!rc) rc = oge_memcpy(c, o, b.d_offs + lo, (m + 1) * 8, 4);
+            DevBuf r(c), o(c);
+            int rc = r.alloc(bytes + 64);
+            if (!rc) rc = o.alloc((m + 1) * 8);
+            if (!rc && bytes) rc = oge_memcpy(c, r.as<void>(), b.d_recs + boff[g], bytes, 4);
+            if (!rc) rc = oge_memcpy(c, o.as<void>(), b.d_offs + lo, (m + 1) * 8, 4);
             if (rc) why[g] = oge_last_error(c);
             // the offsets stay absolute: the records pointer is shifted back by the range's first one
             const int rd = rc ? oge_sort_markdup_dist(cc.comms[g], nullptr, nullptr, 0, n_ref, sort ? 1 : 0, opts, &dout, &doff, &no, &nd)
-                              : oge_sort_markdup_dist(cc.comms[g], (const uint8_t *)r - boff[g], (const uint64_t *)o, m, n_ref,
+                              : oge_sort_markdup_dist(cc.comms[g], r.as<uint8_t>() - boff[g], o.as<uint64_t>(), m, n_ref,
                                                       sort ? 1 : 0, opts, &dout, &doff, &no, &nd);
             if (!rc && rd) why[g] = oge_last_error(c);
             rcs[g] = rc ? rc : rd;
-            if (r) oge_dev_free(c, r);
-            if (o) oge_dev_free(c, o);
             sl[g] = {c, dout, doff, no};
             nds[g] = nd;
         });
@@ -204,11 +206,11 @@ int AlgorithmModule::runChain(ChainContext &cc) {
             continue;
         }
         if (verbose_) fprintf(stderr, "[openge] running %s on %llu records\n", m->name(), (unsigned long long)b.n);
-        const auto t0 = std::chrono::steady_clock::now();
+        const auto t0 = clk();
         int rc = m->runInternal(cc, b);
         if (verbose_)
             fprintf(stderr, "[openge] %s: %.3f s\n", m->name(),
-                    std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+                    sec(t0, clk()));
         if (rc) {
             cc.free_device(b);
             return rc;
@@ -222,190 +224,23 @@ int AlgorithmModule::runChain(ChainContext &cc) {
 }
 
 // ----------------------------------------------------------------------------------- FileReader
-// The input read into host memory on helper threads while the process is still bringing up HIP (r06: the CLI
-// starts this before oge_ctx_create, ~0.2 s, and the reader then only copies it up).  One file of 64 MiB to
-// 8 GiB; OGE_PREFETCH=0 turns it off.
-namespace {
-struct Prefetch {
-    std::string path;
-    uint64_t size = 0;
-    bytevec data;
-    std::thread th;
-    bool ok = false;
-};
-Prefetch *g_prefetch = nullptr;
-bool g_prefetch_used = false;  // (the reader's -v line says so)
-}  // namespace
-
-void prefetch_input(const std::string &path) {
-    const char *e = getenv("OGE_PREFETCH");
-    if ((e && *e == '0') || g_prefetch) return;
-    struct stat st;
-    const char *mn = getenv("OGE_PREFETCH_MIN");  // smallest file prefetched (bytes; tests lower it)
-    const long long pmin = mn && *mn ? atoll(mn) : (64ll << 20);
-    if (stat(path.c_str(), &st) || !S_ISREG(st.st_mode) || st.st_size < pmin || st.st_size < 1 || st.st_size > (8ll << 30)) return;
-    auto *P = new Prefetch();
-    P->path = path;
-    P->size = (uint64_t)st.st_size;
-    P->th = std::thread([P]() {
-        const int fd = open(P->path.c_str(), O_RDONLY);
-        if (fd < 0) return;
-        const uint64_t Z = P->size;
-        try {
-            P->data.reserve(Z + 16);
-            want_huge_pages(P->data.data(), Z + 16);
-            P->data.resize(Z + 16);  // uninitialised: the reads below fill it
-        } catch (const std::bad_alloc &) {
-            close(fd);
-            return;
-        }
-        memset(P->data.data() + Z, 0, 16);
-        std::atomic<bool> bad(false);
-        const int T = 8;
-        std::vector<std::thread> ts;
-        for (int k = 0; k < T; ++k)
-            ts.emplace_back([&, k]() {
-                uint64_t o = Z * (uint64_t)k / T;
-                const uint64_t end = Z * (uint64_t)(k + 1) / T;
-                while (o < end) {
-                    const ssize_t r = pread(fd, P->data.data() + o, end - o, (off_t)o);
-                    if (r <= 0) {
-                        bad = true;
-                        return;
-                    }
-                    o += (uint64_t)r;
-                }
-            });
-        for (auto &t : ts) t.join();
-        close(fd);
-        P->ok = !bad;
-    });
-    g_prefetch = P;
-}
-
-// the prefetched bytes of `path` when they match a file of Z bytes (the helper joined first)
-static bool take_prefetch(const std::string &path, uint64_t Z, bytevec &out) {
-    Prefetch *P = g_prefetch;
-    if (!P || P->path != path) return false;
-    g_prefetch = nullptr;
-    if (P->th.joinable()) P->th.join();
-    const bool ok = P->ok && P->size == Z;
-    if (ok) out = std::move(P->data);
-    delete P;
-    return ok;
-}
-
-// The file streamed into HBM through two page-locked buffers (parallel preads of one while the other
-// is copied), indexed on the device: no host copy of the whole file to allocate, fault in and unmap
-// (a 29 GB file's unmap alone took 1.5 s).  Returns 2 when it does not apply (small files, inputs
-// close to the HBM size, a framing the device index rejects) -- the caller then takes the host path.
-static int stream_to_device(ChainContext &cc, const std::string &path, void **dz_out, uint64_t *zbytes) {
-    const int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) return 2;
-    struct stat stt;
-    const char *mn = getenv("OGE_STREAM_MIN");  // smallest file streamed (bytes; tests lower it)
-    const long long smin = mn && *mn ? atoll(mn) : (64ll << 20);
-    if (fstat(fd, &stt) || !S_ISREG(stt.st_mode) || stt.st_size < smin || stt.st_size < 1) {
-        close(fd);
-        return 2;
-    }
-    const uint64_t Z = (uint64_t)stt.st_size;
-    uint64_t fr = 0, tot = 0;
-    if (oge_mem_info(cc.ctx, &fr, &tot) || Z / 10 * 40 > fr) {  // leave the host path to size what follows
-        close(fd);
-        return 2;
-    }
-    void *dz = nullptr, *hb[2] = {nullptr, nullptr};
-    {
-        bytevec pre;
-        if (take_prefetch(path, Z, pre)) {  // read while HIP came up: one copy from the helper's buffer
-            g_prefetch_used = true;
-            const bool ok = !oge_dev_alloc(cc.ctx, Z + 16, &dz) && !oge_memcpy(cc.ctx, dz, pre.data(), Z, 1);
-            std::thread([](bytevec v) { v = bytevec(); }, std::move(pre)).detach();  // unmapped beside what follows
-            close(fd);
-            if (!ok) {
-                if (dz) oge_dev_free(cc.ctx, dz);
-                return 2;
-            }
-            *dz_out = dz;
-            *zbytes = Z;
-            return 0;
-        }
-    }
-    const uint64_t CH = getenv("OGE_STREAM_MIN") ? (64ull << 10) : (256ull << 20);  // tests: many small chunks
-    auto cleanup = [&]() {
-        for (void *h : hb)
-            if (h) oge_host_free(cc.ctx, h);
-        close(fd);
-    };
-    if (oge_dev_alloc(cc.ctx, Z + 16, &dz) || oge_host_alloc(cc.ctx, CH, &hb[0]) || oge_host_alloc(cc.ctx, CH, &hb[1])) {
-        if (dz) oge_dev_free(cc.ctx, dz);
-        cleanup();
-        return 2;
-    }
-    const uint64_t nch = (Z + CH - 1) / CH;
-    std::atomic<bool> bad(false);
-    auto read_chunk = [&](uint64_t c) {  // chunk c into hb[c & 1], 8 preads of 32 MB in parallel
-        const uint64_t o0 = c * CH, e0 = std::min(Z, o0 + CH);
-        const uint64_t sl = 32ull << 20, ns = (e0 - o0 + sl - 1) / sl;
-        std::vector<std::thread> ts;
-        for (uint64_t k = 0; k < ns; ++k)
-            ts.emplace_back([&, k]() {
-                uint64_t o = o0 + k * sl;
-                const uint64_t e = std::min(e0, o + sl);
-                while (o < e) {
-                    const ssize_t r = pread(fd, (uint8_t *)hb[c & 1] + (o - o0), e - o, (off_t)o);
-                    if (r <= 0) {
-                        bad = true;
-                        return;
-                    }
-                    o += (uint64_t)r;
-                }
-            });
-        for (auto &t : ts) t.join();
-    };
-    read_chunk(0);
-    for (uint64_t c = 0; c < nch && !bad; ++c) {
-        std::thread next;
-        if (c + 1 < nch) next = std::thread(read_chunk, c + 1);
-        const uint64_t o = c * CH, len = std::min(Z, o + CH) - o;
-        if (oge_memcpy(cc.ctx, (uint8_t *)dz + o, hb[c & 1], len, 1)) bad = true;
-        if (next.joinable()) next.join();
-    }
-    cleanup();
-    if (bad) {
-        oge_dev_free(cc.ctx, dz);
-        return 2;
-    }
-    *dz_out = dz;
-    *zbytes = Z;
-    return 0;
-}
-
 int FileReader::read_device(ChainContext &cc, ReadBatch &b, const std::string &path) {
-    auto clk = [] { return std::chrono::steady_clock::now(); };
-    auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point z) {
-        return std::chrono::duration<double>(z - a).count();
-    };
     const auto t0 = clk();
     const int threads = cc.threads > 0 ? cc.threads : 8;
     bytevec comp;
     std::string err;
-    void *dz = nullptr, *di = nullptr, *dc = nullptr, *dout = nullptr, *doff = nullptr;
-    auto release = [&]() {
-        for (void *p : {dz, di, dc, dout, doff})
-            if (p) oge_dev_free(cc.ctx, p);
-    };
-    uint64_t nb = 0, total = 0, zbytes = 0;
+    LoadedFile z(cc.ctx);
+    DevBuf di(cc.ctx), dc(cc.ctx), dout(cc.ctx), doff(cc.ctx);
+    uint64_t nb = 0, total = 0;
     bool streamed = false;
     if (!getenv("OGE_CHUNK_BYTES") && !(getenv("OGE_READER") && std::string(getenv("OGE_READER")) == "hostcopy") &&
-        stream_to_device(cc, path, &dz, &zbytes) == 0) {
+        file_to_device(cc, path, LOAD_STREAM, z) == 0) {
         // framing index on the device (count, then fill); anything it rejects goes to the host path
-        streamed = oge_bgzf_index_dev(cc.ctx, (const uint8_t *)dz, zbytes, nullptr, nullptr, nullptr, nullptr, 0, &nb) == 0 &&
-                   oge_dev_alloc(cc.ctx, (3 * nb + 1) * 8, &di) == 0 && oge_dev_alloc(cc.ctx, nb * 4 + 4, &dc) == 0;
+        streamed = oge_bgzf_index_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, nullptr, nullptr, nullptr, nullptr, 0, &nb) == 0 &&
+                   di.alloc((3 * nb + 1) * 8) == 0 && dc.alloc(nb * 4 + 4) == 0;
         if (streamed) {
-            uint64_t *dd = (uint64_t *)di;
-            streamed = oge_bgzf_index_dev(cc.ctx, (const uint8_t *)dz, zbytes, dd, dd + nb, dd + 2 * nb, (uint32_t *)dc, nb, &nb) == 0 &&
+            uint64_t *dd = di.as<uint64_t>();
+            streamed = oge_bgzf_index_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, dd, dd + nb, dd + 2 * nb, dc.as<uint32_t>(), nb, &nb) == 0 &&
                        oge_memcpy(cc.ctx, &total, dd + 3 * nb, 8, 2) == 0;
         }
         if (streamed && sink_sorts()) {
@@ -413,13 +248,13 @@ int FileReader::read_device(ChainContext &cc, ReadBatch &b, const std::string &p
             if (oge_mem_info(cc.ctx, &fr, &tot) || total / 10 * 25 > fr) streamed = false;
         }
         if (!streamed) {
-            release();
-            dz = di = dc = nullptr;
+            z.buf.reset(), di.reset(), dc.reset();
             nb = total = 0;
         }
     }
     auto t1 = clk();
     if (!streamed) {
+        prefetch_drop();  // OGE_CHUNK_BYTES / OGE_READER=hostcopy: nobody takes it
         if (!read_file_bytes(path, comp, threads, err)) {
             fprintf(stderr, "openge: error reading %s: %s\n", path.c_str(), err.c_str());
             return -1;
@@ -435,34 +270,21 @@ int FileReader::read_device(ChainContext &cc, ReadBatch &b, const std::string &p
             if (getenv("OGE_CHUNK_BYTES") || (!oge_mem_info(cc.ctx, &fr, &tot) && total / 10 * 25 > fr)) return 1;
         }
         t1 = clk();
-        zbytes = comp.size();
-        if (oge_dev_alloc(cc.ctx, comp.size() + 16, &dz) || oge_dev_alloc(cc.ctx, idx.size() * 8, &di) ||
-            oge_dev_alloc(cc.ctx, crc.size() * 4 + 4, &dc)) {
-            release();
-            return cc.fail("device allocation");
-        }
-        if (oge_memcpy(cc.ctx, dz, comp.data(), comp.size(), 1) || oge_memcpy(cc.ctx, di, idx.data(), idx.size() * 8, 1) ||
-            oge_memcpy(cc.ctx, dc, crc.data(), crc.size() * 4, 1)) {
-            release();
+        z.zbytes = comp.size();
+        if (z.buf.alloc(comp.size() + 16) || di.alloc(idx.size() * 8) || dc.alloc(crc.size() * 4 + 4)) return cc.fail("device allocation");
+        if (oge_memcpy(cc.ctx, z.buf.as<void>(), comp.data(), comp.size(), 1) || oge_memcpy(cc.ctx, di.as<void>(), idx.data(), idx.size() * 8, 1) ||
+            oge_memcpy(cc.ctx, dc.as<void>(), crc.data(), crc.size() * 4, 1))
             return cc.fail("host->device copy");
-        }
     }
-    if (oge_dev_alloc(cc.ctx, total + 64, &dout)) {
-        release();
-        return cc.fail("device allocation");
-    }
+    if (dout.alloc(total + 64)) return cc.fail("device allocation");
     const auto t2 = clk();
-    const uint64_t *dd = (const uint64_t *)di;
-    if (nb && oge_bgzf_inflate_dev(cc.ctx, (const uint8_t *)dz, zbytes, dd, dd + nb, dd + 2 * nb, (const uint32_t *)dc, nb,
-                                   (uint8_t *)dout)) {
-        release();
+    const uint64_t *dd = di.as<uint64_t>();
+    if (nb && oge_bgzf_inflate_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, dd, dd + nb, dd + 2 * nb, dc.as<uint32_t>(), nb, dout.as<uint8_t>()))
         return 1;
-    }
     double t_kern = -1;
     if (verbose_) oge_ctx_timing(cc.ctx, "bgzf_inflate", &t_kern);  // synchronises: the kernels' own time
     const auto t2b = clk();
-    oge_dev_free(cc.ctx, dz);
-    dz = nullptr;
+    z.buf.reset();
     // the host path's copy of the compressed file (29 GB at 150M reads) takes ~1.5 s to unmap: on a
     // thread of its own, beside the device stages that follow
     if (!comp.empty()) std::thread([](bytevec v) { v = bytevec(); }, std::move(comp)).detach();
@@ -473,32 +295,21 @@ int FileReader::read_device(ChainContext &cc, ReadBatch &b, const std::string &p
     size_t rec_base = 0;
     for (uint64_t pre = std::min<uint64_t>(total, 1 << 20);; pre = std::min<uint64_t>(total, pre * 8)) {
         std::vector<uint8_t> h(pre);
-        if (pre && oge_memcpy(cc.ctx, h.data(), dout, pre, 2)) {
-            release();
-            return cc.fail("device->host copy");
-        }
+        if (pre && oge_memcpy(cc.ctx, h.data(), dout.as<void>(), pre, 2)) return cc.fail("device->host copy");
         f = BamFile();
         if (bam_parse_header(h.data(), pre, f, err, &rec_base)) break;
-        if (pre == total) {
-            release();
-            return 1;
-        }
+        if (pre == total) return 1;
     }
     uint64_t n = 0;
-    if (oge_bam_record_offsets_dev(cc.ctx, (const uint8_t *)dout, rec_base, total, (int32_t)f.ref_names.size(), nullptr, 0, &n) ||
-        oge_dev_alloc(cc.ctx, (n + 1) * 8, &doff) ||
-        oge_bam_record_offsets_dev(cc.ctx, (const uint8_t *)dout, rec_base, total, (int32_t)f.ref_names.size(), (uint64_t *)doff,
-                                   n + 1, &n)) {
-        release();
+    if (oge_bam_record_offsets_dev(cc.ctx, dout.as<uint8_t>(), rec_base, total, (int32_t)f.ref_names.size(), nullptr, 0, &n) ||
+        doff.alloc((n + 1) * 8) ||
+        oge_bam_record_offsets_dev(cc.ctx, dout.as<uint8_t>(), rec_base, total, (int32_t)f.ref_names.size(), doff.as<uint64_t>(), n + 1, &n))
         return 1;
-    }
-    oge_dev_free(cc.ctx, di);
-    oge_dev_free(cc.ctx, dc);
     b.header = f.header;
     b.ref_names = f.ref_names;
     b.n = n;
-    b.d_recs = (uint8_t *)dout;
-    b.d_offs = (uint64_t *)doff;
+    b.d_recs = (uint8_t *)dout.release();
+    b.d_offs = (uint64_t *)doff.release();
     b.d_bytes = total;
     b.dev_valid = true;
     b.host_valid = false;
@@ -506,53 +317,10 @@ int FileReader::read_device(ChainContext &cc, ReadBatch &b, const std::string &p
         fprintf(stderr,
                 "[openge] FileReader (device%s): file %.3f s, upload %.3f s, inflate %.3f s (kernels %.3f s, release of the "
                 "compressed copies %.3f s), records %.3f s\n",
-                streamed ? (g_prefetch_used ? ", prefetched + device index" : ", streamed + device index") : "", sec(t0, t1),
+                streamed ? (z.prefetched ? ", prefetched + device index" : ", streamed + device index") : "", sec(t0, t1),
                 sec(t1, t2), sec(t2, t3), t_kern / 1e3, sec(t2b, t3),
                 sec(t3, clk()));
     return 0;
-}
-
-// Bytes [off, off + len) of the open file into device memory dst (rank ctx's stream): parallel preads
-// into one of two page-locked buffers while the other is copied.  0 = ok.
-static int read_range_to_device(oge_ctx *ctx, int fd, uint64_t off, uint64_t len, uint8_t *dst) {
-    if (!len) return 0;
-    const uint64_t CH = std::min<uint64_t>(len, 128ull << 20);
-    void *hb[2] = {nullptr, nullptr};
-    if (oge_host_alloc(ctx, CH, &hb[0]) || oge_host_alloc(ctx, CH, &hb[1])) {
-        for (void *h : hb)
-            if (h) oge_host_free(ctx, h);
-        return -1;
-    }
-    std::atomic<bool> bad(false);
-    const uint64_t nch = (len + CH - 1) / CH;
-    auto read_chunk = [&](uint64_t c) {
-        const uint64_t o0 = c * CH, e0 = std::min(len, o0 + CH), sl = 16ull << 20, ns = (e0 - o0 + sl - 1) / sl;
-        std::vector<std::thread> ts;
-        for (uint64_t k = 0; k < ns; ++k)
-            ts.emplace_back([&, k]() {
-                uint64_t o = o0 + k * sl;
-                const uint64_t e = std::min(e0, o + sl);
-                while (o < e) {
-                    const ssize_t r = pread(fd, (uint8_t *)hb[c & 1] + (o - o0), e - o, (off_t)(off + o));
-                    if (r <= 0) {
-                        bad = true;
-                        return;
-                    }
-                    o += (uint64_t)r;
-                }
-            });
-        for (auto &t : ts) t.join();
-    };
-    read_chunk(0);
-    for (uint64_t c = 0; c < nch && !bad; ++c) {
-        std::thread next;
-        if (c + 1 < nch) next = std::thread(read_chunk, c + 1);
-        const uint64_t o = c * CH, l = std::min(len, o + CH) - o;
-        if (oge_memcpy(ctx, dst + o, hb[c & 1], l, 1)) bad = true;
-        if (next.joinable()) next.join();
-    }
-    for (void *h : hb) oge_host_free(ctx, h);
-    return bad ? -1 : 0;
 }
 
 // True when the next module takes per-rank input shards (run_ranks: the coordinate ReadSorter, or a
@@ -568,18 +336,12 @@ bool FileReader::sink_takes_shards() const {
 // inflating the whole file.  Returns 1 when the file cannot be opened or decoded this way (the
 // whole-file readers take over and report it).
 int FileReader::read_sharded(ChainContext &cc, ReadBatch &b, const std::string &path) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const int fd = open(path.c_str(), O_RDONLY);
+    const auto t0 = clk();
+    const OwnedFd file(open(path.c_str(), O_RDONLY));
+    const int fd = file.fd;
     struct stat stt;
-    if (fd < 0) return 1;
-    if (fstat(fd, &stt) || !S_ISREG(stt.st_mode)) {
-        close(fd);
-        return 1;
-    }
-    if (cc.init_ranks()) {
-        close(fd);
-        return -1;
-    }
+    if (fd < 0 || fstat(fd, &stt) || !S_ISREG(stt.st_mode)) return 1;
+    if (cc.init_ranks()) return -1;
     const int G = cc.gpus;
     const uint64_t Z = (uint64_t)stt.st_size;
     std::vector<ReadBatch::Slice> sh(G);
@@ -594,28 +356,27 @@ int FileReader::read_sharded(ChainContext &cc, ReadBatch &b, const std::string &
             oge_ctx *c = cc.rank_ctx[g];
             const uint64_t a = Z * (uint64_t)g / (uint64_t)G, bnd = Z * (uint64_t)(g + 1) / (uint64_t)G;
             const uint64_t end = std::min<uint64_t>(Z, bnd + 65536), len = end - a;
-            void *dz = nullptr;
-            const auto r0 = std::chrono::steady_clock::now();
-            int rc = oge_dev_alloc(c, len + 64, &dz);
-            if (!rc && read_range_to_device(c, fd, a, len, (uint8_t *)dz)) rc = OGE_ERR_IO;
+            DevBuf dz(c);
+            const auto r0 = clk();
+            int rc = dz.alloc(len + 64);
+            // 128 MiB chunks read as 16 MiB slices
+            if (!rc && range_to_device(c, fd, a, len, dz.as<uint8_t>(), std::min<uint64_t>(len, 128ull << 20), 16ull << 20)) rc = OGE_ERR_IO;
             if (rc) why[g] = rc == OGE_ERR_IO ? std::string("read failed") : std::string(oge_last_error(c));
-            const auto r1 = std::chrono::steady_clock::now();
+            const auto r1 = clk();
             const uint8_t *recs = nullptr;
             const uint64_t *offs = nullptr;
             uint64_t n = 0, hl = 0;
             // a rank whose read failed still takes part, with no buffer: its argument error fails every rank
-            const int rd = oge_bgzf_decode_shard(cc.comms[g], rc ? nullptr : (const uint8_t *)dz, len, bnd - a, &recs, &offs, &n,
+            const int rd = oge_bgzf_decode_shard(cc.comms[g], rc ? nullptr : dz.as<uint8_t>(), len, bnd - a, &recs, &offs, &n,
                                                  g == 0 ? hdr.data() : nullptr, g == 0 ? hdr.size() : 0, g == 0 ? &hl : nullptr);
             if (!rc && rd) why[g] = oge_last_error(c);
             rcs[g] = rc ? rc : rd;
             if (g == 0) hlen = hl;
-            if (dz) oge_dev_free(c, dz);
             sh[g] = {c, const_cast<uint8_t *>(recs), const_cast<uint64_t *>(offs), n};
-            t_read[g] = std::chrono::duration<double>(r1 - r0).count();
-            t_dec[g] = std::chrono::duration<double>(std::chrono::steady_clock::now() - r1).count();
+            t_read[g] = sec(r0, r1);
+            t_dec[g] = sec(r1, clk());
         });
     for (auto &t : ts) t.join();
-    close(fd);
     // a file the sharded decode rejects goes to the whole-file readers, which report format errors with
     // the reference's messages (the ranks failed together, so their communicators are still in step)
     for (int g = 0; g < G; ++g)
@@ -643,8 +404,7 @@ int FileReader::read_sharded(ChainContext &cc, ReadBatch &b, const std::string &
                      (unsigned long long)nb, (unsigned long long)sh[g].n);
             per += tmp;
         }
-        fprintf(stderr, "[openge] FileReader (sharded over %d ranks): %.3f s%s\n", G,
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), per.c_str());
+        fprintf(stderr, "[openge] FileReader (sharded over %d ranks): %.3f s%s\n", G, sec(t0, clk()), per.c_str());
     }
     return 0;
 }
@@ -668,6 +428,7 @@ int FileReader::runInternal(ChainContext &cc, ReadBatch &b) {
         const int r = read_device(cc, b, files_[0]);
         if (r <= 0) return r;  // 1: fall through to the host reader (it reports format errors)
     }
+    prefetch_drop();  // the host reader reads the file itself
     for (size_t i = 0; i < files_.size(); ++i) {
         const std::string path = files_[i] == "stdin" ? "/dev/stdin" : files_[i];
         BamFile f;
@@ -863,21 +624,16 @@ int Filter::runInternal(ChainContext &cc, ReadBatch &b) {
         }
     }
     if (cc.to_device(b)) return -1;
-    void *out = nullptr, *out_off = nullptr;
-    if (oge_dev_alloc(cc.ctx, b.d_bytes + 64, &out) || oge_dev_alloc(cc.ctx, (b.n + 1) * 8, &out_off))
-        return cc.fail("device allocation");
+    DevBuf out(cc.ctx), out_off(cc.ctx);
+    if (out.alloc(b.d_bytes + 64) || out_off.alloc((b.n + 1) * 8)) return cc.fail("device allocation");
     uint64_t m = 0, bytes = 0;
-    int rc = oge_filter_records_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &o, (uint8_t *)out, (uint64_t *)out_off, &m);
-    if (!rc) rc = oge_memcpy(cc.ctx, &bytes, (uint64_t *)out_off + m, 8, 2);
+    int rc = oge_filter_records_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &o, out.as<uint8_t>(), out_off.as<uint64_t>(), &m);
+    if (!rc) rc = oge_memcpy(cc.ctx, &bytes, out_off.as<uint64_t>() + m, 8, 2);
     if (!rc) rc = oge_ctx_sync(cc.ctx);
-    if (rc) {
-        oge_dev_free(cc.ctx, out);
-        oge_dev_free(cc.ctx, out_off);
-        return cc.fail("Filter");
-    }
+    if (rc) return cc.fail("Filter");
     cc.free_device(b);
-    b.d_recs = (uint8_t *)out;
-    b.d_offs = (uint64_t *)out_off;
+    b.d_recs = (uint8_t *)out.release();
+    b.d_offs = (uint64_t *)out_off.release();
     b.d_bytes = bytes;
     b.n = m;
     b.dev_valid = true;
@@ -909,13 +665,13 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
         MdOpts m;
         if (md) markdup_opts(b, md->compatNonverbose, md->splitChains, m);
         uint64_t nd = 0;
-        const auto t0 = std::chrono::steady_clock::now();
+        const auto t0 = clk();
         if (run_ranks(cc, b, true, md ? &m.o : nullptr, &nd)) return -1;
         if (md) md->duplicates = nd;
         b.header.sort_order = order_;
         if (verbose_)
             fprintf(stderr, "[openge] ReadSorter: %d ranks, %.3f s\n", cc.gpus,
-                    std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+                    sec(t0, clk()));
         return 0;
     }
     if (order_ == BamHeaderModel::COORDINATE && use_chunked(cc, b)) {
@@ -950,35 +706,34 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
         b.header.sort_order = order_;
         return 0;
     }
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = clk();
     if (cc.to_device(b)) return -1;
-    const auto t1 = std::chrono::steady_clock::now();
-    void *perm = nullptr, *out = nullptr, *out_off = nullptr;
-    if (oge_dev_alloc(cc.ctx, b.n * 4 + 4, &perm) || oge_dev_alloc(cc.ctx, b.d_bytes + 64, &out) ||
-        oge_dev_alloc(cc.ctx, (b.n + 1) * 8, &out_off))
-        return cc.fail("device allocation");
+    const auto t1 = clk();
+    DevBuf perm_buf(cc.ctx), out_buf(cc.ctx), off_buf(cc.ctx);
+    if (perm_buf.alloc(b.n * 4 + 4) || out_buf.alloc(b.d_bytes + 64) || off_buf.alloc((b.n + 1) * 8)) return cc.fail("device allocation");
+    uint32_t *perm = perm_buf.as<uint32_t>();
+    uint8_t *out = out_buf.as<uint8_t>();
+    uint64_t *out_off = off_buf.as<uint64_t>();
     if (verbose_) oge_ctx_sync(cc.ctx);
-    const auto t1a = std::chrono::steady_clock::now();
+    const auto t1a = clk();
     int rc;
     if (order_ == BamHeaderModel::QUERYNAME) {  // -b; a MarkDuplicates sink then runs on its own
-        rc = oge_sort_name_dev(cc.ctx, b.d_recs, b.d_offs, b.n, (uint32_t *)perm);
-        if (!rc) rc = oge_gather_records_dev(cc.ctx, b.d_recs, b.d_offs, (uint32_t *)perm, b.n, (uint8_t *)out, (uint64_t *)out_off);
+        rc = oge_sort_name_dev(cc.ctx, b.d_recs, b.d_offs, b.n, perm);
+        if (!rc) rc = oge_gather_records_dev(cc.ctx, b.d_recs, b.d_offs, perm, b.n, out, out_off);
     } else if (md) {  // mergesort -M: one fused device pipeline (sort, dedup, gather with 0x400 applied)
         MdOpts m;
         markdup_opts(b, md->compatNonverbose, md->splitChains, m);
         uint64_t nd = 0;
-        rc = oge_sort_markdup_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &m.o, (uint32_t *)perm, (uint8_t *)out,
-                                  (uint64_t *)out_off, &nd);
+        rc = oge_sort_markdup_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &m.o, perm, out, out_off, &nd);
         md->duplicates = nd;
     } else {
-        rc = oge_sort_coord_dev(cc.ctx, b.d_recs, b.d_offs, b.n, (int32_t)b.ref_names.size(), (uint32_t *)perm);
-        if (!rc) rc = oge_gather_records_dev(cc.ctx, b.d_recs, b.d_offs, (uint32_t *)perm, b.n, (uint8_t *)out, (uint64_t *)out_off);
+        rc = oge_sort_coord_dev(cc.ctx, b.d_recs, b.d_offs, b.n, (int32_t)b.ref_names.size(), perm);
+        if (!rc) rc = oge_gather_records_dev(cc.ctx, b.d_recs, b.d_offs, perm, b.n, out, out_off);
     }
     if (!rc) rc = oge_ctx_sync(cc.ctx);
     if (verbose_) {
-        fprintf(stderr, "[openge] ReadSorter: host->device %.3f s, output allocation %.3f s, device pipeline %.3f s\n",
-                std::chrono::duration<double>(t1 - t0).count(), std::chrono::duration<double>(t1a - t1).count(),
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t1a).count());
+        fprintf(stderr, "[openge] ReadSorter: host->device %.3f s, output allocation %.3f s, device pipeline %.3f s\n", sec(t0, t1),
+                sec(t1, t1a), sec(t1a, clk()));
         std::string st;  // HIP-event stage times of the device pipeline (ms)
         for (const char *s : {"input_pass", "sort_radix", "sort_ties", "meta_gather", "md_matejoin", "md_pairs", "md_frags",
                               "md_apply", "gather_offsets", "gather_records", "name_sort"}) {
@@ -987,15 +742,10 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
         }
         fprintf(stderr, "[openge] ReadSorter stages (ms):%s\n", st.c_str());
     }
-    oge_dev_free(cc.ctx, perm);
-    if (rc) {
-        oge_dev_free(cc.ctx, out);
-        oge_dev_free(cc.ctx, out_off);
-        return cc.fail("ReadSorter");
-    }
+    if (rc) return cc.fail("ReadSorter");
     cc.free_device(b);
-    b.d_recs = (uint8_t *)out;
-    b.d_offs = (uint64_t *)out_off;
+    b.d_recs = (uint8_t *)out_buf.release();
+    b.d_offs = (uint64_t *)off_buf.release();
     b.dev_valid = true;
     b.host_valid = false;
     b.header.sort_order = order_;  // read_sorter.cpp:257-258
@@ -1018,15 +768,12 @@ int MarkDuplicates::runInternal(ChainContext &cc, ReadBatch &b) {
         return 0;
     }
     if (cc.to_device(b)) return -1;
-    void *dup = nullptr;
-    if (oge_dev_alloc(cc.ctx, b.n + 1, &dup)) return cc.fail("device allocation");
+    DevBuf dup(cc.ctx);
+    if (dup.alloc(b.n + 1)) return cc.fail("device allocation");
     MdOpts m;
     markdup_opts(b, compatNonverbose, splitChains, m);
     uint64_t nd = 0;
-    int rc = oge_markdup_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &m.o, (uint8_t *)dup, 1, &nd);
-    if (!rc) rc = oge_ctx_sync(cc.ctx);
-    oge_dev_free(cc.ctx, dup);
-    if (rc) return cc.fail("MarkDuplicates");
+    if (oge_markdup_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &m.o, dup.as<uint8_t>(), 1, &nd) || oge_ctx_sync(cc.ctx)) return cc.fail("MarkDuplicates");
     duplicates = nd;
     b.host_valid = false;
     b.drop_duplicates = removeDuplicates;
@@ -1062,7 +809,7 @@ static int realign_ranks(ChainContext &cc, ReadBatch &b, const std::string &ht, 
 }
 
 int LocalRealignment::runInternal(ChainContext &cc, ReadBatch &b) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = clk();
     if (cc.to_host(b)) return -1;
     cc.free_device(b);
     const std::string ht = b.header.to_string();
@@ -1071,11 +818,11 @@ int LocalRealignment::runInternal(ChainContext &cc, ReadBatch &b) {
     oge_realign_opts_init(&o);
     o.threads = cc.threads;
     oge_realign_result *r = nullptr;
-    const auto t1 = std::chrono::steady_clock::now();
+    const auto t1 = clk();
     if (oge_localrealign(cc.ctx, ht.data(), ht.size(), b.recs.data(), b.offs.data(), b.n, reference_.c_str(),
                          intervals_.c_str(), &o, &r))
         return cc.fail("LocalRealignment");
-    const auto t2 = std::chrono::steady_clock::now();
+    const auto t2 = clk();
     uint64_t bytes = 0;
     const uint8_t *rp = oge_realign_result_records(r, &bytes);
     const uint64_t *op = oge_realign_result_offsets(r);
@@ -1086,27 +833,24 @@ int LocalRealignment::runInternal(ChainContext &cc, ReadBatch &b) {
     // -- and the writer compresses it with the host codec (zlib-class level 6, as the reference writes).
     uint64_t fr = 0, tot = 0;
     const uint64_t base = n ? op[0] : 0, len = n ? op[n] - base : 0;
-    void *dr = nullptr, *dof = nullptr;
+    DevBuf dr(cc.ctx), dof(cc.ctx);
     bool up = n && write_device_forced() && !bgzf_host_codec_forced() && !oge_mem_info(cc.ctx, &fr, &tot) &&
               2 * len + (n + 1) * 16 + (256ull << 20) < fr;
     if (up) {
         std::vector<uint64_t> ro(op, op + n + 1);
         for (auto &x : ro) x -= base;
-        up = !oge_dev_alloc(cc.ctx, len + 64, &dr) && !oge_dev_alloc(cc.ctx, (n + 1) * 8, &dof) &&
-             !oge_memcpy(cc.ctx, dr, rp + base, len, 1) && !oge_memcpy(cc.ctx, dof, ro.data(), (n + 1) * 8, 1);
+        up = !dr.alloc(len + 64) && !dof.alloc((n + 1) * 8) && !oge_memcpy(cc.ctx, dr.as<void>(), rp + base, len, 1) &&
+             !oge_memcpy(cc.ctx, dof.as<void>(), ro.data(), (n + 1) * 8, 1);
         if (up) {
             b.recs.clear();
             b.recs.shrink_to_fit();
             b.offs.clear();
             b.offs.shrink_to_fit();
-            b.d_recs = (uint8_t *)dr;
-            b.d_offs = (uint64_t *)dof;
+            b.d_recs = (uint8_t *)dr.release();
+            b.d_offs = (uint64_t *)dof.release();
             b.d_bytes = len;
             b.dev_valid = true;
             b.host_valid = false;
-        } else {
-            if (dr) oge_dev_free(cc.ctx, dr);
-            if (dof) oge_dev_free(cc.ctx, dof);
         }
     }
     if (verbose) fprintf(stderr, "[openge] LocalRealignment: %s\n", oge_realign_result_stats(r));
@@ -1119,15 +863,11 @@ int LocalRealignment::runInternal(ChainContext &cc, ReadBatch &b) {
     }
     (void)rp;
     b.n = n;
-    const auto t3 = std::chrono::steady_clock::now();
+    const auto t3 = clk();
     oge_realign_result_free(r);
-    if (verbose) {
-        auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point z) {
-            return std::chrono::duration<double>(z - a).count();
-        };
+    if (verbose)
         fprintf(stderr, "[openge] LocalRealignment: records to host %.3f s, realign %.3f s, result %s %.3f s, release %.3f s\n",
-                sec(t0, t1), sec(t1, t2), up ? "to the device" : "host copy", sec(t2, t3), sec(t3, std::chrono::steady_clock::now()));
-    }
+                sec(t0, t1), sec(t1, t2), up ? "to the device" : "host copy", sec(t2, t3), sec(t3, clk()));
     return 0;
 }
 
@@ -1167,13 +907,28 @@ FileFormat FileWriter::getFileFormat() const {
     return fmt == FORMAT_UNKNOWN ? default_format_ : fmt;
 }
 
+// offs[0] and offs[n] of records that sit back to back: the byte range of their stream (0, 0 when n = 0)
+static int stream_ends(oge_ctx *ctx, const uint64_t *offs, uint64_t n, uint64_t ends[2]) {
+    ends[0] = ends[1] = 0;
+    return n && (oge_memcpy(ctx, &ends[0], offs, 8, 2) || oge_memcpy(ctx, &ends[1], offs + n, 8, 2));
+}
+
+// -r / -R: the records without OGE_F_DUP compacted into kept / kept_off (`bytes` of records at most), and
+// recs / offs / n repointed at them.  Returns what failed, for ChainContext::fail, or nullptr.
+template <class R, class O>
+static const char *drop_dups(oge_ctx *ctx, R **recs, O **offs, uint64_t *n, uint64_t bytes, DevBuf &kept, DevBuf &kept_off) {
+    uint64_t m = 0;
+    if (kept.need(bytes + 64) || kept_off.need((*n + 1) * 8)) return "device allocation";
+    if (oge_drop_flagged_dev(ctx, *recs, *offs, *n, OGE_F_DUP, kept.as<uint8_t>(), kept_off.as<uint64_t>(), &m)) return "FileWriter: drop duplicates";
+    *recs = kept.as<uint8_t>();
+    *offs = kept_off.as<uint64_t>();
+    *n = m;
+    return nullptr;
+}
+
 // Device-resident records -> SAM or FASTQ text.  Everything that can fail on the records (an unknown tag
 // type, a host line that does not format) fails before the output is opened.
 int FileWriter::write_text(ChainContext &cc, ReadBatch &b, FileFormat fmt) {
-    auto clk = [] { return std::chrono::steady_clock::now(); };
-    auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point z) {
-        return std::chrono::duration<double>(z - a).count();
-    };
     const bool to_stdout = filename_ == "stdout" || filename_ == "-";
     const char *why = !b.slices.empty() ? "--gpus"
                       : b.produce       ? "output larger than device memory (chunked sort)"
@@ -1189,27 +944,10 @@ int FileWriter::write_text(ChainContext &cc, ReadBatch &b, FileFormat fmt) {
     uint8_t *recs = b.d_recs;
     uint64_t *offs = b.d_offs;
     uint64_t n = b.n;
-    void *kept = nullptr, *kept_off = nullptr, *d_toff = nullptr, *d_mark = nullptr, *d_out = nullptr, *hz[2] = {nullptr, nullptr};
-    std::thread wr;
-    auto release = [&]() {
-        if (wr.joinable()) wr.join();
-        for (void *p : {kept, kept_off, d_toff, d_mark, d_out})
-            if (p) oge_dev_free(cc.ctx, p);
-        for (void *h : hz)
-            if (h) oge_host_free(cc.ctx, h);
-    };
-    auto bail = [&](const char *what) {
-        release();
-        return cc.fail(what);
-    };
-    if (b.drop_duplicates && n) {
-        uint64_t m = 0;
-        if (oge_dev_alloc(cc.ctx, b.d_bytes + 64, &kept) || oge_dev_alloc(cc.ctx, (n + 1) * 8, &kept_off)) return bail("device allocation");
-        if (oge_drop_flagged_dev(cc.ctx, recs, offs, n, OGE_F_DUP, (uint8_t *)kept, (uint64_t *)kept_off, &m)) return bail("FileWriter: drop duplicates");
-        recs = (uint8_t *)kept;
-        offs = (uint64_t *)kept_off;
-        n = m;
-    }
+    DevBuf kept(cc.ctx), kept_off(cc.ctx), d_toff(cc.ctx), d_mark(cc.ctx), d_out(cc.ctx);
+    PinBuf hz[2] = {PinBuf(cc.ctx), PinBuf(cc.ctx)};
+    if (b.drop_duplicates && n)
+        if (const char *what = drop_dups(cc.ctx, &recs, &offs, &n, b.d_bytes, kept, kept_off)) return cc.fail(what);
     std::string names;
     std::vector<uint32_t> name_off{0};
     for (auto &sq : b.header.sq) {
@@ -1224,28 +962,27 @@ int FileWriter::write_text(ChainContext &cc, ReadBatch &b, FileFormat fmt) {
     o.ref_names = names.data();
     o.ref_name_off = name_off.data();
     uint64_t total = 0, n_host = 0;
-    if (oge_dev_alloc(cc.ctx, (n + 1) * 8, &d_toff) || oge_dev_alloc(cc.ctx, n + 1, &d_mark)) return bail("device allocation");
-    if (oge_text_size_dev(cc.ctx, recs, offs, n, &o, (uint64_t *)d_toff, (uint8_t *)d_mark, &total, &n_host)) return bail("FileWriter");
+    if (d_toff.alloc((n + 1) * 8) || d_mark.alloc(n + 1)) return cc.fail("device allocation");
+    if (oge_text_size_dev(cc.ctx, recs, offs, n, &o, d_toff.as<uint64_t>(), d_mark.as<uint8_t>(), &total, &n_host)) return cc.fail("FileWriter");
     std::vector<uint64_t> toff(n + 1);
-    if (oge_memcpy(cc.ctx, toff.data(), d_toff, (n + 1) * 8, 2)) return bail("device->host copy");
+    if (oge_memcpy(cc.ctx, toff.data(), d_toff.as<void>(), (n + 1) * 8, 2)) return cc.fail("device->host copy");
     // the lines the device leaves out, formatted here from the records' bytes
     std::vector<uint64_t> host_rec;
     std::vector<std::string> host_line;
     if (n_host) {
         std::vector<uint8_t> mark(n);
-        if (oge_memcpy(cc.ctx, mark.data(), d_mark, n, 2)) return bail("device->host copy");
+        if (oge_memcpy(cc.ctx, mark.data(), d_mark.as<void>(), n, 2)) return cc.fail("device->host copy");
         std::vector<uint8_t> rb;
         std::vector<char> line;
         for (uint64_t i = 0; i < n; ++i) {
             if (!mark[i]) continue;
             uint64_t at = 0, len = 0;
             uint32_t bs = 0;
-            if (oge_memcpy(cc.ctx, &at, offs + i, 8, 2) || oge_memcpy(cc.ctx, &bs, recs + at, 4, 2)) return bail("device->host copy");
+            if (oge_memcpy(cc.ctx, &at, offs + i, 8, 2) || oge_memcpy(cc.ctx, &bs, recs + at, 4, 2)) return cc.fail("device->host copy");
             rb.resize((size_t)bs + 4);
-            if (oge_memcpy(cc.ctx, rb.data(), recs + at, rb.size(), 2)) return bail("device->host copy");
+            if (oge_memcpy(cc.ctx, rb.data(), recs + at, rb.size(), 2)) return cc.fail("device->host copy");
             line.resize(16 * rb.size() + 1024);
             if (oge_text_host_line(rb.data(), rb.size(), &o, line.data(), line.size(), &len)) {
-                release();
                 fprintf(stderr, "openge: FileWriter: record %llu: %s\n", (unsigned long long)i, oge_last_error(nullptr));
                 return -1;
             }
@@ -1266,11 +1003,10 @@ int FileWriter::write_text(ChainContext &cc, ReadBatch &b, FileFormat fmt) {
         cut.push_back(e);
     }
     const size_t nchunks = cut.size() - 1;
-    if (cap && (oge_dev_alloc(cc.ctx, cap + 16, &d_out) || oge_host_alloc(cc.ctx, cap, &hz[0]) || (nchunks > 1 && oge_host_alloc(cc.ctx, cap, &hz[1]))))
-        return bail("FileWriter: buffers");
-    FILE *f = to_stdout ? stdout : fopen(filename_.c_str(), "wb");
+    if (cap && (d_out.alloc(cap + 16) || hz[0].alloc(cap) || (nchunks > 1 && hz[1].alloc(cap)))) return cc.fail("FileWriter: buffers");
+    OutFile file(to_stdout ? stdout : fopen(filename_.c_str(), "wb"));
+    FILE *f = file.f;
     if (!f) {
-        release();
         fprintf(stderr, "Error opening %s file to write.\n", fmt == FORMAT_SAM ? "SAM" : "FASTQ");
         return -1;
     }
@@ -1287,29 +1023,23 @@ int FileWriter::write_text(ChainContext &cc, ReadBatch &b, FileFormat fmt) {
     double t_dev = 0, t_d2h = 0, t_wait = 0;
     size_t hk = 0;  // the next host line
     int k = 0;
+    JoinThread wr;  // the last owner declared: joined before the file is closed and the buffers are freed
     for (size_t c = 0; c < nchunks && !failed; ++c, k ^= 1) {
         const uint64_t s = cut[c], e = cut[c + 1], bytes = toff[e] - toff[s];
         auto t = clk();
-        if (oge_text_emit_dev(cc.ctx, recs, offs, (const uint64_t *)d_toff, s, e - s, &o, (uint8_t *)d_out, cap) || oge_ctx_sync(cc.ctx)) {
-            release();
-            if (f != stdout) fclose(f);
+        if (oge_text_emit_dev(cc.ctx, recs, offs, d_toff.as<uint64_t>(), s, e - s, &o, d_out.as<uint8_t>(), cap) || oge_ctx_sync(cc.ctx))
             return cc.fail("FileWriter: text on the device");
-        }
         t_dev += sec(t, clk());
         t = clk();
-        if (wr.joinable()) wr.join();  // the buffer written two chunks ago is free again
+        wr.join();  // the buffer written two chunks ago is free again
         t_wait += sec(t, clk());
         t = clk();
-        if (bytes && oge_memcpy(cc.ctx, hz[k], d_out, bytes, 2)) {
-            release();
-            if (f != stdout) fclose(f);
-            return cc.fail("device->host copy");
-        }
+        if (bytes && oge_memcpy(cc.ctx, hz[k].as<void>(), d_out.as<void>(), bytes, 2)) return cc.fail("device->host copy");
         t_d2h += sec(t, clk());
         const size_t h0 = hk;
         while (hk < host_rec.size() && host_rec[hk] < e) ++hk;
         const size_t h1 = hk;
-        const uint8_t *hp = (const uint8_t *)hz[k];
+        const uint8_t *hp = hz[k].as<uint8_t>();
         wr = std::thread([&, hp, s, bytes, h0, h1]() {
             uint64_t done = 0;
             for (size_t j = h0; j < h1; ++j) {
@@ -1322,10 +1052,11 @@ int FileWriter::write_text(ChainContext &cc, ReadBatch &b, FileFormat fmt) {
         });
     }
     auto t = clk();
-    if (wr.joinable()) wr.join();
+    wr.join();
     t_wait += sec(t, clk());
-    release();
-    if (f != stdout ? fclose(f) != 0 : fflush(f) != 0) failed = true;
+    for (DevBuf *p : {&kept, &kept_off, &d_toff, &d_mark, &d_out}) p->reset();  // freed here only so that the total below times it
+    hz[0].reset(), hz[1].reset();
+    if (file.close() != 0) failed = true;
     if (failed) {
         fprintf(stderr, "openge: error writing %s: %s\n", filename_.c_str(), strerror(errno));
         return -1;
@@ -1363,10 +1094,6 @@ static void fix_bins(ReadBatch &b, int threads) {
 // two page-locked buffers and are written by a background thread while the next segment is
 // deflated and copied.  Timings: device deflate, device->host, and time spent waiting for the disk.
 int FileWriter::write_device(ChainContext &cc, ReadBatch &b, BgzfWriter &w, double *t_dev, double *t_d2h, double *t_wait) {
-    auto clk = [] { return std::chrono::steady_clock::now(); };
-    auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point z) {
-        return std::chrono::duration<double>(z - a).count();
-    };
     *t_dev = *t_d2h = *t_wait = 0;
     if (const char *f = getenv("OGE_TEST_FAIL"); f && !strcmp(f, "write_device")) {  // test hook: a failed device write
         fprintf(stderr, "openge: FileWriter: injected failure (OGE_TEST_FAIL=write_device)\n");
@@ -1375,37 +1102,14 @@ int FileWriter::write_device(ChainContext &cc, ReadBatch &b, BgzfWriter &w, doub
     uint8_t *recs = b.d_recs;
     uint64_t *offs = b.d_offs;
     uint64_t n = b.n;
-    void *kept = nullptr, *kept_off = nullptr, *dz = nullptr, *hz[2] = {nullptr, nullptr};
-    std::thread wr;
-    auto release = [&]() {
-        if (wr.joinable()) wr.join();
-        if (kept) oge_dev_free(cc.ctx, kept);
-        if (kept_off) oge_dev_free(cc.ctx, kept_off);
-        if (dz) oge_dev_free(cc.ctx, dz);
-        for (void *h : hz)
-            if (h) oge_host_free(cc.ctx, h);
-    };
+    DevBuf kept(cc.ctx), kept_off(cc.ctx), dz(cc.ctx);
+    PinBuf hz[2] = {PinBuf(cc.ctx), PinBuf(cc.ctx)};
+    JoinThread wr;  // the last owner declared: joined before the buffers it writes from are freed
     auto t = clk();
-    if (b.drop_duplicates && n) {
-        if (oge_dev_alloc(cc.ctx, b.d_bytes + 64, &kept) || oge_dev_alloc(cc.ctx, (n + 1) * 8, &kept_off)) {
-            release();
-            return cc.fail("device allocation");
-        }
-        uint64_t m = 0;
-        if (oge_drop_flagged_dev(cc.ctx, recs, offs, n, OGE_F_DUP, (uint8_t *)kept, (uint64_t *)kept_off, &m)) {
-            release();
-            return cc.fail("FileWriter: drop duplicates");
-        }
-        recs = (uint8_t *)kept;
-        offs = (uint64_t *)kept_off;
-        n = m;
-    }
-    uint64_t ends[2] = {0, 0};
-    if (n && (oge_fix_bins_dev(cc.ctx, recs, offs, n) || oge_memcpy(cc.ctx, &ends[0], offs, 8, 2) ||
-              oge_memcpy(cc.ctx, &ends[1], offs + n, 8, 2))) {
-        release();
-        return cc.fail("FileWriter: bins");
-    }
+    if (b.drop_duplicates && n)
+        if (const char *what = drop_dups(cc.ctx, &recs, &offs, &n, b.d_bytes, kept, kept_off)) return cc.fail(what);
+    uint64_t ends[2];
+    if ((n && oge_fix_bins_dev(cc.ctx, recs, offs, n)) || stream_ends(cc.ctx, offs, n, ends)) return cc.fail("FileWriter: bins");
     *t_dev += sec(t, clk());
     const uint64_t len = ends[1] - ends[0];
     // segments of 1024-32768 payloads (67 MB - 2.14 GB of records), about an eighth of the stream: the
@@ -1418,11 +1122,7 @@ int FileWriter::write_device(ChainContext &cc, ReadBatch &b, BgzfWriter &w, doub
     const uint64_t seg = std::min(len, kSeg);
     const uint64_t cap = oge_bgzf_bound(seg);
     t = clk();
-    if (len && (oge_dev_alloc(cc.ctx, cap, &dz) || oge_host_alloc(cc.ctx, cap, &hz[0]) ||
-                (len > seg && oge_host_alloc(cc.ctx, cap, &hz[1])))) {
-        release();
-        return cc.fail("FileWriter: buffers");
-    }
+    if (len && (dz.alloc(cap) || hz[0].alloc(cap) || (len > seg && hz[1].alloc(cap)))) return cc.fail("FileWriter: buffers");
     if (getenv("OGE_WRITE_TRACE")) fprintf(stderr, "[openge] FileWriter: buffers %.3f s\n", sec(t, clk()));
     w.write_compressed(nullptr, 0);  // flush the header as blocks of its own
     // --index: the block table of the file, from the BSIZE fields of the bytes that go to it (the header's
@@ -1434,30 +1134,23 @@ int FileWriter::write_device(ChainContext &cc, ReadBatch &b, BgzfWriter &w, doub
         const uint64_t sl = std::min(seg, len - s0);
         uint64_t zb = 0;
         t = clk();
-        if (oge_bgzf_deflate_dev(cc.ctx, recs + ends[0] + s0, sl, std::max(0, std::min(9, level_)), (uint8_t *)dz, cap, &zb) ||
-            oge_ctx_sync(cc.ctx)) {
-            release();
+        if (oge_bgzf_deflate_dev(cc.ctx, recs + ends[0] + s0, sl, std::max(0, std::min(9, level_)), dz.as<uint8_t>(), cap, &zb) ||
+            oge_ctx_sync(cc.ctx))
             return cc.fail("FileWriter: BGZF on the device");
-        }
         *t_dev += sec(t, clk());
         t = clk();
-        if (wr.joinable()) wr.join();  // the buffer written two segments ago is free again
+        wr.join();  // the buffer written two segments ago is free again
         *t_wait += sec(t, clk());
         t = clk();
-        if (zb && oge_memcpy(cc.ctx, hz[k], dz, zb, 2)) {
-            release();
-            return cc.fail("device->host copy");
-        }
+        if (zb && oge_memcpy(cc.ctx, hz[k].as<void>(), dz.as<void>(), zb, 2)) return cc.fail("device->host copy");
         *t_d2h += sec(t, clk());
-        const uint8_t *hp = (const uint8_t *)hz[k];
+        const uint8_t *hp = hz[k].as<uint8_t>();
         if (index_) {
             uint64_t nb = 0;
             const int rc = oge_bgzf_index(hp, zb, nullptr, nullptr, nullptr, nullptr, 0, &nb);
             std::vector<uint64_t> d0(nb + 1), uo(nb + 1);
-            if ((rc != OGE_OK && rc != OGE_ERR_ARG) || oge_bgzf_index(hp, zb, d0.data(), nullptr, uo.data(), nullptr, nb, &nb)) {
-                release();
+            if ((rc != OGE_OK && rc != OGE_ERR_ARG) || oge_bgzf_index(hp, zb, d0.data(), nullptr, uo.data(), nullptr, nb, &nb))
                 return cc.fail("FileWriter: index of the written blocks");
-            }
             for (uint64_t i = 0; i < nb; ++i) {  // the device writer's blocks have 18-byte headers
                 ix_cstart.push_back(ix_z + d0[i] - 18);
                 ix_uoff.push_back(ix_u + uo[i]);
@@ -1468,17 +1161,17 @@ int FileWriter::write_device(ChainContext &cc, ReadBatch &b, BgzfWriter &w, doub
         wr = std::thread([&w, hp, zb]() { w.write_compressed(hp, zb); });
     }
     t = clk();
-    if (wr.joinable()) wr.join();
+    wr.join();
     *t_wait += sec(t, clk());
-    if (index_) {  // before release() frees the kept records
+    if (index_) {  // from the kept records
         ix_uoff.push_back(ix_u);
         ix_cstart.push_back(ix_z);
         const uint64_t nblk = ix_uoff.size() - 1;
-        void *tab = nullptr;
+        DevBuf tab(cc.ctx);
         const uint8_t *d_bai = nullptr;
         uint64_t bb = 0;
-        int rc = oge_dev_alloc(cc.ctx, 2 * (nblk + 1) * 8, &tab);
-        uint64_t *dt = (uint64_t *)tab;
+        int rc = tab.alloc(2 * (nblk + 1) * 8);
+        uint64_t *dt = tab.as<uint64_t>();
         if (!rc) rc = oge_memcpy(cc.ctx, dt, ix_uoff.data(), (nblk + 1) * 8, 1);
         if (!rc) rc = oge_memcpy(cc.ctx, dt + nblk + 1, ix_cstart.data(), (nblk + 1) * 8, 1);
         if (!rc) rc = oge_bai_build_dev(cc.ctx, recs, offs, n, (int32_t)b.header.sq.size(), index_hdr_u_, dt, dt + nblk + 1, nblk, &d_bai, &bb);
@@ -1486,14 +1179,10 @@ int FileWriter::write_device(ChainContext &cc, ReadBatch &b, BgzfWriter &w, doub
             bai_.resize(bb);
             rc = oge_memcpy(cc.ctx, bai_.data(), d_bai, bb, 2);
         }
-        if (tab) oge_dev_free(cc.ctx, tab);
-        if (rc) {
-            release();
-            return cc.fail("FileWriter: index");
-        }
+        if (rc) return cc.fail("FileWriter: index");
     }
     t = clk();
-    release();
+    kept.reset(), kept_off.reset(), dz.reset(), hz[0].reset(), hz[1].reset();  // freed here only so that the trace times it
     if (getenv("OGE_WRITE_TRACE")) fprintf(stderr, "[openge] FileWriter: release %.3f s\n", sec(t, clk()));
     return 0;
 }
@@ -1504,12 +1193,13 @@ int FileWriter::write_device(ChainContext &cc, ReadBatch &b, BgzfWriter &w, doub
 int FileWriter::write_slices(ChainContext &cc, ReadBatch &b, BgzfWriter &w) {
     const int G = (int)b.slices.size();
     struct Out {
-        void *host = nullptr;
+        PinBuf host;
         uint64_t zb = 0;
         int rc = 0;
         std::string why;
     };
-    std::vector<Out> outs(G);
+    std::vector<Out> outs;
+    for (auto &s : b.slices) outs.push_back(Out{PinBuf(s.ctx)});
     const int level = std::max(0, std::min(9, level_));
     const bool drop = b.drop_duplicates;
     std::vector<std::thread> ts;
@@ -1520,29 +1210,19 @@ int FileWriter::write_slices(ChainContext &cc, ReadBatch &b, BgzfWriter &w) {
             oge_ctx *c = s.ctx;
             uint8_t *recs = s.d_recs;
             uint64_t *offs = s.d_offs, n = s.n;
-            void *kept = nullptr, *kept_off = nullptr, *dz = nullptr;
-            int rc = 0;
-            if (drop && n) {
-                rc = oge_dev_alloc(c, (n + 1) * 8, &kept_off);
-                uint64_t e = 0, m = 0;
-                if (!rc) rc = oge_memcpy(c, &e, offs + n, 8, 2);
-                if (!rc) rc = oge_dev_alloc(c, e + 64, &kept);
-                if (!rc) rc = oge_drop_flagged_dev(c, recs, offs, n, OGE_F_DUP, (uint8_t *)kept, (uint64_t *)kept_off, &m);
-                recs = (uint8_t *)kept;
-                offs = (uint64_t *)kept_off;
-                n = m;
-            }
+            DevBuf kept(c), kept_off(c), dz(c);
             uint64_t ends[2] = {0, 0};
-            if (!rc && n) rc = oge_memcpy(c, &ends[0], offs, 8, 2) || oge_memcpy(c, &ends[1], offs + n, 8, 2);
+            int rc = 0;
+            if (drop && n)  // kept is sized by the slice's own stream end
+                rc = stream_ends(c, offs, n, ends) || drop_dups(c, &recs, &offs, &n, ends[1], kept, kept_off) != nullptr;
+            if (!rc) rc = stream_ends(c, offs, n, ends);
             const uint64_t len = ends[1] - ends[0], cap = oge_bgzf_bound(len);
-            if (!rc && len) rc = oge_dev_alloc(c, cap, &dz);
-            if (!rc && len) rc = oge_bgzf_deflate_dev(c, recs + ends[0], len, level, (uint8_t *)dz, cap, &o.zb);
-            if (!rc && o.zb) rc = oge_host_alloc(c, o.zb, &o.host);
-            if (!rc && o.zb) rc = oge_memcpy(c, o.host, dz, o.zb, 2);
+            if (!rc && len) rc = dz.alloc(cap);
+            if (!rc && len) rc = oge_bgzf_deflate_dev(c, recs + ends[0], len, level, dz.as<uint8_t>(), cap, &o.zb);
+            if (!rc && o.zb) rc = o.host.alloc(o.zb);
+            if (!rc && o.zb) rc = oge_memcpy(c, o.host.as<void>(), dz.as<void>(), o.zb, 2);
             if (rc) o.why = oge_last_error(c);
             o.rc = rc;
-            for (void *p : {kept, kept_off, dz})
-                if (p) oge_dev_free(c, p);
         });
     w.write_compressed(nullptr, 0);  // the header's blocks first
     int ret = 0;
@@ -1552,9 +1232,9 @@ int FileWriter::write_slices(ChainContext &cc, ReadBatch &b, BgzfWriter &w) {
             fprintf(stderr, "openge: FileWriter: rank %d: %s\n", g, outs[g].why.c_str());
             ret = -1;
         } else if (!ret && outs[g].zb) {
-            w.write_compressed((const uint8_t *)outs[g].host, outs[g].zb);
+            w.write_compressed(outs[g].host.as<uint8_t>(), outs[g].zb);
         }
-        if (outs[g].host) oge_host_free(b.slices[g].ctx, outs[g].host);
+        outs[g].host.reset();
     }
     return ret;
 }
@@ -1565,47 +1245,20 @@ int FileWriter::write_ranges(ChainContext &cc, ReadBatch &b, BgzfWriter &w) {
     w.write_compressed(nullptr, 0);  // the header's blocks first
     const int level = std::max(0, std::min(9, level_));
     const bool drop = b.drop_duplicates;
-    struct Buf {
-        oge_ctx *c;
-        void *p = nullptr;
-        uint64_t cap = 0;
-        bool host = false;
-        int need(uint64_t bytes) {
-            if (bytes <= cap) return 0;
-            if (p) host ? oge_host_free(c, p) : oge_dev_free(c, p);
-            p = nullptr;
-            cap = 0;
-            const int rc = host ? oge_host_alloc(c, bytes, &p) : oge_dev_alloc(c, bytes, &p);
-            if (!rc) cap = bytes;
-            return rc;
-        }
-        ~Buf() {
-            if (p) host ? oge_host_free(c, p) : oge_dev_free(c, p);
-        }
-    } kept{cc.ctx}, kept_off{cc.ctx}, dz{cc.ctx}, hz{cc.ctx};
-    hz.host = true;
+    DevBuf kept(cc.ctx), kept_off(cc.ctx), dz(cc.ctx);  // grown to the largest range, kept between ranges
+    PinBuf hz(cc.ctx);
     auto sink = [&](const uint8_t *recs, const uint64_t *offs, uint64_t n) -> int {
-        uint64_t ends[2] = {0, 0};
-        if (n && (oge_memcpy(cc.ctx, &ends[0], offs, 8, 2) || oge_memcpy(cc.ctx, &ends[1], offs + n, 8, 2))) return -1;
-        if (drop && n) {
-            uint64_t m = 0;
-            if (kept.need(ends[1] + 64) || kept_off.need((n + 1) * 8) ||
-                oge_drop_flagged_dev(cc.ctx, recs, offs, n, OGE_F_DUP, (uint8_t *)kept.p, (uint64_t *)kept_off.p, &m))
-                return -1;
-            recs = (const uint8_t *)kept.p;
-            offs = (const uint64_t *)kept_off.p;
-            n = m;
-            ends[0] = ends[1] = 0;
-            if (n && (oge_memcpy(cc.ctx, &ends[0], offs, 8, 2) || oge_memcpy(cc.ctx, &ends[1], offs + n, 8, 2))) return -1;
-        }
+        uint64_t ends[2];
+        if (stream_ends(cc.ctx, offs, n, ends)) return -1;
+        if (drop && n && (drop_dups(cc.ctx, &recs, &offs, &n, ends[1], kept, kept_off) || stream_ends(cc.ctx, offs, n, ends))) return -1;
         const uint64_t len = ends[1] - ends[0];
         if (!len) return 0;
         const uint64_t cap = oge_bgzf_bound(len);
         uint64_t zb = 0;
-        if (dz.need(cap) || oge_bgzf_deflate_dev(cc.ctx, recs + ends[0], len, level, (uint8_t *)dz.p, cap, &zb) || hz.need(zb) ||
-            oge_memcpy(cc.ctx, hz.p, dz.p, zb, 2))
+        if (dz.need(cap) || oge_bgzf_deflate_dev(cc.ctx, recs + ends[0], len, level, dz.as<uint8_t>(), cap, &zb) || hz.need(zb) ||
+            oge_memcpy(cc.ctx, hz.as<void>(), dz.as<void>(), zb, 2))
             return -1;
-        w.write_compressed((const uint8_t *)hz.p, zb);
+        w.write_compressed(hz.as<uint8_t>(), zb);
         return 0;
     };
     if (b.produce(cc, sink)) return -1;
@@ -1613,10 +1266,6 @@ int FileWriter::write_ranges(ChainContext &cc, ReadBatch &b, BgzfWriter &w) {
 }
 
 int FileWriter::runInternal(ChainContext &cc, ReadBatch &b) {
-    auto clk = [] { return std::chrono::steady_clock::now(); };
-    auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point z) {
-        return std::chrono::duration<double>(z - a).count();
-    };
     const FileFormat fmt = getFileFormat();
     if (fmt == FORMAT_SAM || fmt == FORMAT_FASTQ) return write_text(cc, b, fmt);
     if (fmt != FORMAT_BAM) {  // file_writer.cpp:192-195
@@ -1663,7 +1312,8 @@ int FileWriter::runInternal(ChainContext &cc, ReadBatch &b) {
     const auto t2 = clk();
     BamHeaderModel h = b.header;
     if (!program_line_.empty()) add_program_record(h, program_line_);  // file_writer.cpp:76-89
-    FILE *f = filename_ == "stdout" || filename_ == "-" ? stdout : fopen(filename_.c_str(), "wb");
+    OutFile file(filename_ == "stdout" || filename_ == "-" ? stdout : fopen(filename_.c_str(), "wb"));
+    FILE *f = file.f;
     if (!f) {
         fprintf(stderr, "Error opening BAM file to write.\n");
         return -1;
@@ -1681,8 +1331,7 @@ int FileWriter::runInternal(ChainContext &cc, ReadBatch &b) {
         }
         if (on_device) {
             if (produced ? write_ranges(cc, b, w) : sliced ? write_slices(cc, b, w) : write_device(cc, b, w, &t_dev, &t_d2h, &t_wait)) {
-                w.abandon();  // no EOF block and no write into the FILE closed below
-                if (f != stdout) fclose(f);
+                w.abandon();  // no EOF block and no write into the FILE closed at the return
                 return -1;
             }
             w.close();
@@ -1709,7 +1358,7 @@ int FileWriter::runInternal(ChainContext &cc, ReadBatch &b) {
         w.close();
         write_ok = w.ok();
     }
-    if (f != stdout ? fclose(f) != 0 : fflush(f) != 0) write_ok = false;
+    if (file.close() != 0) write_ok = false;
     if (!write_ok) {  // a full disk or a closed pipe must not look like success
         fprintf(stderr, "openge: error writing %s: %s\n", filename_.c_str(), strerror(errno));
         return -1;
@@ -1734,25 +1383,27 @@ int FileWriter::runInternal(ChainContext &cc, ReadBatch &b) {
     return 0;
 }
 
+// index / stats / count / coverage: the whole file in HBM (64 bytes of slack); `what` names a failed upload,
+// timed: the -v line of the qc commands
+static int load_whole(ChainContext &cc, const std::string &path, const char *what, bool timed, LoadedFile &z) {
+    const int rc = file_to_device(cc, path, LOAD_WHOLE, z);
+    if (rc == -2) return cc.fail(what);
+    if (!rc && timed && cc.verbose) fprintf(stderr, "[openge] read %.3f s, upload %.3f s\n", z.t_read, z.t_upload);
+    return rc;
+}
+
 int index_bam_file(ChainContext &cc, const std::string &path, const std::string &out) {
-    bytevec z;
-    std::string err;
-    if (!read_file_bytes(path, z, cc.threads > 0 ? cc.threads : 8, err)) {
-        fprintf(stderr, "openge: %s: %s\n", path.c_str(), err.c_str());
-        return -1;
-    }
-    void *dz = nullptr;
+    LoadedFile z(cc.ctx);
+    if (load_whole(cc, path, "index", false, z)) return -1;
     const uint8_t *d_bai = nullptr;
     uint64_t bb = 0;
     std::vector<uint8_t> img;
-    int rc = oge_dev_alloc(cc.ctx, z.size() + 64, &dz);
-    if (!rc) rc = oge_memcpy(cc.ctx, dz, z.data(), z.size(), 1);
-    if (!rc) rc = oge_bam_index_dev(cc.ctx, (const uint8_t *)dz, z.size(), &d_bai, &bb);
+    int rc = oge_bam_index_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, &d_bai, &bb);
     if (!rc) {
         img.resize(bb);
         rc = oge_memcpy(cc.ctx, img.data(), d_bai, bb, 2);
     }
-    if (dz) oge_dev_free(cc.ctx, dz);
+    z.buf.reset();
     if (rc) return cc.fail("index");
     FILE *f = fopen(out.c_str(), "wb");
     const bool ok = f && fwrite(img.data(), 1, img.size(), f) == img.size();
@@ -1766,29 +1417,6 @@ int index_bam_file(ChainContext &cc, const std::string &path, const std::string 
 
 // ---- stats / count / coverage ------------------------------------------------------------------------
 namespace {
-
-std::chrono::steady_clock::time_point clk() { return std::chrono::steady_clock::now(); }
-double sec(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point z) {
-    return std::chrono::duration<double>(z - a).count();
-}
-
-// the file's bytes in HBM (64 bytes of slack); the caller frees *dz
-int upload_bam(ChainContext &cc, const std::string &path, void **dz, uint64_t *zbytes) {
-    bytevec z;
-    std::string err;
-    const auto t0 = clk();
-    if (!read_file_bytes(path, z, cc.threads > 0 ? cc.threads : 8, err)) {
-        fprintf(stderr, "openge: %s: %s\n", path.c_str(), err.c_str());
-        return -1;
-    }
-    const auto t1 = clk();
-    int rc = oge_dev_alloc(cc.ctx, z.size() + 64, dz);
-    if (!rc) rc = oge_memcpy(cc.ctx, *dz, z.data(), z.size(), 1);
-    if (rc) return cc.fail("upload");
-    *zbytes = z.size();
-    if (cc.verbose) fprintf(stderr, "[openge] read %.3f s, upload %.3f s\n", sec(t0, t1), sec(t1, clk()));
-    return 0;
-}
 
 void report_stages(ChainContext &cc, const char *reduce, double t_format) {
     if (!cc.verbose) return;
@@ -1841,18 +1469,14 @@ struct TsvWriter {
 }  // namespace
 
 int stats_bam_file(ChainContext &cc, const std::string &path, bool inserts, bool lengths) {
-    void *dz = nullptr;
-    uint64_t zb = 0;
-    if (upload_bam(cc, path, &dz, &zb)) {
-        if (dz) oge_dev_free(cc.ctx, dz);
-        return -1;
-    }
+    LoadedFile z(cc.ctx);
+    if (load_whole(cc, path, "upload", true, z)) return -1;
     oge_bam_stats s;
     const uint32_t *d_len = nullptr;
     const uint64_t *d_cnt = nullptr;
     std::vector<uint32_t> len;
     std::vector<uint64_t> cnt;
-    int rc = oge_bam_stats_dev(cc.ctx, (const uint8_t *)dz, zb, (inserts ? OGE_STATS_INSERTS : 0) | (lengths ? OGE_STATS_LENGTHS : 0), &s,
+    int rc = oge_bam_stats_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, (inserts ? OGE_STATS_INSERTS : 0) | (lengths ? OGE_STATS_LENGTHS : 0), &s,
                                &d_len, &d_cnt);
     if (!rc && lengths && s.n_lengths) {
         len.resize(s.n_lengths);
@@ -1860,7 +1484,7 @@ int stats_bam_file(ChainContext &cc, const std::string &path, bool inserts, bool
         rc = oge_memcpy(cc.ctx, len.data(), d_len, s.n_lengths * 4, 2);
         if (!rc) rc = oge_memcpy(cc.ctx, cnt.data(), d_cnt, s.n_lengths * 8, 2);
     }
-    oge_dev_free(cc.ctx, dz);
+    z.buf.reset();
     if (rc) return cc.fail("stats");
     const auto t0 = clk();
     auto line = [](const char *label, uint64_t v, uint64_t of) {
@@ -1907,15 +1531,10 @@ int stats_bam_file(ChainContext &cc, const std::string &path, bool inserts, bool
 }
 
 int count_bam_file(ChainContext &cc, const std::string &path) {
-    void *dz = nullptr;
-    uint64_t zb = 0, n = 0;
-    if (upload_bam(cc, path, &dz, &zb)) {
-        if (dz) oge_dev_free(cc.ctx, dz);
-        return -1;
-    }
-    const int rc = oge_bam_count_dev(cc.ctx, (const uint8_t *)dz, zb, &n);
-    oge_dev_free(cc.ctx, dz);
-    if (rc) return cc.fail("count");
+    LoadedFile z(cc.ctx);
+    uint64_t n = 0;
+    if (load_whole(cc, path, "upload", true, z)) return -1;
+    if (oge_bam_count_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, &n)) return cc.fail("count");
     printf("%llu\n", (unsigned long long)n);
     if (fflush(stdout) != 0 || ferror(stdout)) {
         fprintf(stderr, "openge: error writing to stdout\n");
@@ -1925,20 +1544,17 @@ int count_bam_file(ChainContext &cc, const std::string &path) {
 }
 
 int coverage_bam_file(ChainContext &cc, const std::string &path, const std::string &out, int binsize, bool omit_uncovered) {
-    void *dz = nullptr;
-    uint64_t zb = 0, nb = 0, skipped = 0;
-    if (upload_bam(cc, path, &dz, &zb)) {
-        if (dz) oge_dev_free(cc.ctx, dz);
-        return -1;
-    }
+    LoadedFile z(cc.ctx);
+    uint64_t nb = 0, skipped = 0;
+    if (load_whole(cc, path, "upload", true, z)) return -1;
     const uint32_t *d_bins = nullptr;
     int32_t overflow = 0, n_ref = 0;
     const char *names = nullptr;
     const int32_t *lens = nullptr;
     uint64_t names_bytes = 0;
     std::vector<uint32_t> bins;
-    int rc = oge_bam_coverage_dev(cc.ctx, (const uint8_t *)dz, zb, binsize, &d_bins, &nb, &skipped, &overflow);
-    oge_dev_free(cc.ctx, dz);
+    int rc = oge_bam_coverage_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, binsize, &d_bins, &nb, &skipped, &overflow);
+    z.buf.reset();
     if (!rc) rc = oge_ctx_last_refs(cc.ctx, &n_ref, &names, &names_bytes, &lens);
     if (!rc && nb) {
         bins.resize(nb);
