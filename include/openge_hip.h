@@ -602,6 +602,65 @@ int oge_text_host_line(const uint8_t *rec, uint64_t rec_bytes, const oge_text_op
 int oge_text_format(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const uint64_t *rec_off, uint64_t n,
                     const oge_text_opts *opts, uint8_t *out, uint64_t cap, uint64_t *bytes);
 
+/* ---- SAM text in HBM -> BAM records in HBM (SAM input of every command) ---------------------------------
+ * The reference's SamReader::ParseAlignment (util/sam_reader.cpp:313-488) on the device, the inverse of the
+ * text calls above; DESIGN.md section 22.  A line is QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL
+ * and any number of tags XX:T:value, tab separated.  The record stores POS - 1 and PNEXT - 1, TLEN as it is,
+ * bin from POS - 1 and the CIGAR's reference length (CalculateMinimumBin, util/bam_serializer.h:92-116: POS 0
+ * without CIGAR gives 4680); RNAME and RNEXT become refIDs through the contig table of opts (only n_ref,
+ * ref_names and ref_name_off of oge_text_opts are read; of two contigs with one name the first is found): "*"
+ * is -1, "=" as RNEXT the read's own refID, an RNEXT the table does not have is -1 and sets the line's warning
+ * byte (the reference prints "RNext X missing from sequence dictionary"), an RNAME it does not have is an error
+ * whose message begins with the reference's "Rname X missing from sequence dictionary".  CIGAR "*" gives no
+ * ops, otherwise <length below 2^28><one of MIDNSHP=X> up to 65535 times.  SEQ is packed by "=ACMGRSVTWYHKDBN"
+ * in either case (any other character is N), "*" is l_seq 0; QUAL is byte - 33, "*" is l_seq bytes of 0xFF.
+ * Tags: A; i in the reference's smallest type (C for 0..255, c for -128..-1, S up to 65535, s down to -32768,
+ * then I up to 2^32-1, then i); Z and H as their strings; f (strtof) and B:t,v,... (the specification's array)
+ * only on the host: the size pass gives their lines the exact length and marks them, the emit pass stores
+ * every other byte of such a record, and the caller copies oge_sam_host_record's record over it.
+ * Everything else is an error (OGE_ERR_ARG, the message names the 1-based line of the file and the field):
+ * fewer than 11 fields, a line shorter than 10 characters, a number that is not -?[0-9]+ or outside its
+ * field's range (FLAG 0..65535, MAPQ 0..255, POS - 1 and PNEXT - 1 and TLEN in 32 bits, a tag integer in
+ * -2^31..2^32-1), QNAME longer than 254 characters, QUAL of another length than SEQ, a tag not shaped XX:T:,
+ * a type outside AifZHB, more than 65535 CIGAR ops, a line of more than 2^30 characters.  A '\r' is a
+ * character like any other.  The text needs no slack behind its last byte. */
+/* The length of the leading lines that begin with '@' (the header) and their count (may be NULL). */
+int oge_sam_header(const char *text, uint64_t bytes, uint64_t *header_len, uint64_t *header_lines);
+/* Line index of d_text[body_off, bytes) (d_text 4-byte aligned): *n = the lines (a last line without "\n"
+ * is a line, a trailing "\n" adds none).  With d_line_off NULL it only counts; else d_line_off (cap >= n + 1
+ * entries, OGE_ERR_LIMIT otherwise) gets d_line_off[0] = body_off and d_line_off[i + 1] = one past the
+ * position of line i's newline (bytes + 1 for a last line without one), so line i is d_text[d_line_off[i],
+ * d_line_off[i + 1] - 1).  OGE_ERR_LIMIT when n >= 2^32 - 1.  Stage name for oge_ctx_timing: "sam_lines". */
+int oge_sam_lines_dev(oge_ctx *ctx, const uint8_t *d_text, uint64_t bytes, uint64_t body_off, uint64_t *d_line_off, uint64_t cap,
+                      uint64_t *n);
+/* Size pass and scan.  d_rec_off (n + 1 entries): the exclusive scan of the exact record lengths (block_size
+ * field included), host-marked lines included, so the arena has no holes; d_host_mark (n bytes): 1 for a line
+ * with an f or B tag; d_warn (n bytes): 1 for a line whose RNEXT the table does not have.  *total =
+ * d_rec_off[n], *n_host = the marked lines, also the context counter "sam_host_lines"; counters
+ * "sam_wave_lines" / "sam_block_lines": the lines one wave / one workgroup of the kernels takes.  On a bad line
+ * OGE_ERR_ARG: the message names the lowest bad line (1-based in the file: the lines of d_text[0, d_line_off[0])
+ * count) and its field, counters "sam_bad_line" and "sam_bad_code"; d_rec_off, d_host_mark and d_warn are then left
+ * as they were.  The contig
+ * table is uploaded when it differs from the last call's (counter "sam_table_uploads").  Stage name: "sam_size". */
+int oge_sam_size_dev(oge_ctx *ctx, const uint8_t *d_text, const uint64_t *d_line_off, uint64_t n, const oge_text_opts *opts,
+                     uint64_t *d_rec_off, uint8_t *d_host_mark, uint8_t *d_warn, uint64_t *total, uint64_t *n_host);
+/* Emit pass: the records of lines [first, first + count) at d_recs + d_rec_off[i] - d_rec_off[first]; cap >=
+ * d_rec_off[first + count] - d_rec_off[first] (OGE_ERR_LIMIT otherwise, nothing is written).  opts as in the
+ * size call that filled d_rec_off.  Nothing is stored outside a record's own bytes.  Stage name: "sam_emit". */
+int oge_sam_emit_dev(oge_ctx *ctx, const uint8_t *d_text, const uint64_t *d_line_off, const uint64_t *d_rec_off, uint64_t first,
+                     uint64_t count, const oge_text_opts *opts, uint8_t *d_recs, uint64_t cap);
+/* One line's record (line[0, len), no newline) on the host, every tag type included: written to buf when cap
+ * holds it, *len_out = its length (OGE_ERR_LIMIT when cap is smaller, with *len_out set).  OGE_ERR_ARG with
+ * the field's name for a line that does not parse. */
+int oge_sam_host_record(const char *line, uint64_t len, const oge_text_opts *opts, uint8_t *buf, uint64_t cap, uint64_t *len_out);
+/* Host-buffer form: splits the header (*header_len = the bytes of the leading '@' lines), builds the contig
+ * table from its @SQ lines as the header model reads them (oge_bam_header_text's parser; a header it refuses
+ * is OGE_ERR_ARG), uploads, indexes, sizes, emits, builds the marked lines' records on the host and downloads.  *recs (*rec_bytes bytes and 16 bytes of slack), *rec_off (*n + 1 entries) and *warn
+ * (*n bytes, may be NULL) are the context's, valid until its next oge_sam_parse call.  On an error nothing is
+ * handed back (the pointers are NULL, *n is 0). */
+int oge_sam_parse(oge_ctx *ctx, const char *text, uint64_t bytes, uint64_t *header_len, const uint8_t **recs, uint64_t *rec_bytes,
+                  const uint64_t **rec_off, uint64_t *n, const uint8_t **warn);
+
 /* ---- mergesort extras: Filter (-r region / -q mapq) and sort by name (-b) ----------- */
 /* Filter::runInternal's predicate (algorithms/filter.cpp:205-249) with the module's setters
  * (filter.h:34-47).  len = l_seq (BamAlignment::getLength).  A record is kept when

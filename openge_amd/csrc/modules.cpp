@@ -223,6 +223,216 @@ int AlgorithmModule::runChain(ChainContext &cc) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------ SAM input
+// MultiReader::open looks at the first byte of every input (util/read_stream_reader.h:45-85): '@' is SAM.
+static bool file_is_sam(const std::string &path) {
+    const OwnedFd fd(open(path.c_str(), O_RDONLY));
+    struct stat st;
+    char c = 0;
+    return fd.fd >= 0 && !fstat(fd.fd, &st) && S_ISREG(st.st_mode) && pread(fd.fd, &c, 1, 0) == 1 && c == '@';
+}
+
+// The header text of a SAM file through the model bam_parse_header feeds: the same header and contig names as
+// the BAM file of the same reads gives.
+static bool sam_header_model(const std::string &text, BamFile &f, std::string &err) {
+    f.header_text = text;
+    if (!f.header.parse(text, err)) return false;
+    f.ref_names.clear();
+    f.ref_lens.clear();
+    for (auto &s : f.header.sq) {
+        f.ref_names.push_back(s.name);
+        f.ref_lens.push_back((int32_t)s.length);
+    }
+    return true;
+}
+
+struct SamOpts {  // oge_text_opts over the contig names of a header
+    std::string names;
+    std::vector<uint32_t> off;
+    oge_text_opts o;
+    explicit SamOpts(const std::vector<std::string> &ref_names) : off(1, 0) {
+        for (auto &n : ref_names) {
+            names += n;
+            off.push_back((uint32_t)names.size());
+        }
+        o = {OGE_TEXT_SAM, 0, 0, (int32_t)ref_names.size(), names.data(), off.data()};
+    }
+};
+
+// the reference's stderr line for an RNEXT its dictionary does not have (sam_reader.cpp:373)
+static void warn_rnext(const char *line, uint64_t len) {
+    const char *p = line, *end = line + len;
+    for (int k = 0; k < 6 && p; ++k) {
+        p = (const char *)memchr(p, '\t', (size_t)(end - p));
+        if (p) ++p;
+    }
+    if (!p) return;
+    const char *e = (const char *)memchr(p, '\t', (size_t)(end - p));
+    fprintf(stderr, "RNext %.*s missing from sequence dictionary\n", (int)((e ? e : end) - p), p);
+}
+
+// a failed oge_sam_* call: the reference's own line for an unknown RNAME (sam_reader.cpp:360), then ours
+static int sam_fail(ChainContext &cc, const std::string &name) {
+    const std::string m = oge_last_error(cc.ctx);
+    const size_t cut = m.find(" (sam: line ");
+    if (m.compare(0, 6, "Rname ") == 0 && cut != std::string::npos) {
+        fprintf(stderr, "%s\n", m.substr(0, cut).c_str());
+        fprintf(stderr, "openge: error reading %s: %s\n", name.c_str(), m.substr(cut + 2, m.size() - cut - 3).c_str());
+    } else {
+        fprintf(stderr, "openge: error reading %s: %s\n", name.c_str(), m.c_str());
+    }
+    return -1;
+}
+
+// A SAM text in host memory -> a BamFile (records from rec_base 0), parsed on the GPU (oge_sam_parse).
+static int sam_host_file(ChainContext &cc, const std::string &name, const bytevec &text, BamFile &f) {
+    uint64_t hl = 0, rb = 0, n = 0;
+    const uint8_t *recs = nullptr, *warn = nullptr;
+    const uint64_t *offs = nullptr;
+    if (oge_sam_parse(cc.ctx, (const char *)text.data(), text.size(), &hl, &recs, &rb, &offs, &n, &warn)) return sam_fail(cc, name);
+    std::string err;
+    if (!sam_header_model(std::string((const char *)text.data(), hl), f, err)) {
+        fprintf(stderr, "openge: error reading %s: %s\n", name.c_str(), err.c_str());
+        return -1;
+    }
+    f.rec_base = 0;
+    f.data.assign(recs, recs + rb);
+    f.offsets.assign(offs, offs + n);
+    uint64_t p = hl;
+    for (uint64_t i = 0; i < n; ++i) {  // the lines in file order, only to name the unknown mates
+        const void *nl = memchr(text.data() + p, '\n', text.size() - p);
+        const uint64_t e = nl ? (uint64_t)((const uint8_t *)nl - text.data()) : text.size();
+        if (warn[i]) warn_rnext((const char *)text.data() + p, e - p);
+        p = e + 1;
+    }
+    return 0;
+}
+
+// SAM text resident in HBM (4-byte aligned) -> the batch's records in HBM: the header from a prefix, then the
+// line index, the size pass and the emit pass (oge_sam_*_dev); the few lines with an f or B tag are fetched,
+// built on the host and copied to their places.  need_sort_room: the HBM check the BAM reader makes in front
+// of a ReadSorter, here over the text plus the records; a text that does not fit is refused, not spilled.
+static int sam_device_records(ChainContext &cc, const std::string &name, const uint8_t *d_text, uint64_t bytes, bool need_sort_room, ReadBatch &b,
+                              std::vector<int32_t> *ref_lens = nullptr) {
+    std::string head;
+    uint64_t hl = 0;
+    for (uint64_t pre = std::min<uint64_t>(bytes, 1 << 20);; pre = std::min<uint64_t>(bytes, pre * 8)) {
+        head.resize(pre);
+        if (pre && oge_memcpy(cc.ctx, &head[0], d_text, pre, 2)) return cc.fail("device->host copy");
+        oge_sam_header(head.data(), pre, &hl, nullptr);
+        if (hl < pre || pre == bytes) break;
+    }
+    BamFile f;
+    std::string err;
+    if (!sam_header_model(head.substr(0, hl), f, err)) {
+        fprintf(stderr, "openge: error reading %s: %s\n", name.c_str(), err.c_str());
+        return -1;
+    }
+    const SamOpts so(f.ref_names);
+    uint64_t n = 0, total = 0, n_host = 0;
+    DevBuf dlo(cc.ctx), dro(cc.ctx), dmark(cc.ctx), dwarn(cc.ctx), drecs(cc.ctx);
+    if (oge_sam_lines_dev(cc.ctx, d_text, bytes, hl, nullptr, 0, &n)) return sam_fail(cc, name);
+    if (dlo.alloc((n + 1) * 8) || dro.alloc((n + 1) * 8) || dmark.alloc(n + 1) || dwarn.alloc(n + 1)) return cc.fail("device allocation");
+    if (oge_sam_lines_dev(cc.ctx, d_text, bytes, hl, dlo.as<uint64_t>(), n + 1, &n) ||
+        oge_sam_size_dev(cc.ctx, d_text, dlo.as<uint64_t>(), n, &so.o, dro.as<uint64_t>(), dmark.as<uint8_t>(), dwarn.as<uint8_t>(), &total, &n_host))
+        return sam_fail(cc, name);
+    uint64_t fr = 0, tot = 0;
+    if ((need_sort_room && !oge_mem_info(cc.ctx, &fr, &tot) && total / 10 * 25 > fr) || drecs.alloc(total + 64)) {
+        fprintf(stderr, "openge: error reading %s: the SAM text (%llu bytes) and its records (%llu bytes) do not fit in device memory; "
+                "SAM input larger than HBM is not provided\n", name.c_str(), (unsigned long long)bytes, (unsigned long long)total);
+        return -1;
+    }
+    if (oge_sam_emit_dev(cc.ctx, d_text, dlo.as<uint64_t>(), dro.as<uint64_t>(), 0, n, &so.o, drecs.as<uint8_t>(), total)) return sam_fail(cc, name);
+    std::vector<uint8_t> mark(n), warn(n);
+    if (n && (oge_memcpy(cc.ctx, mark.data(), dmark.as<void>(), n, 2) || oge_memcpy(cc.ctx, warn.data(), dwarn.as<void>(), n, 2)))
+        return cc.fail("device->host copy");
+    // the marked and the warned lines: both offset tables come down once; their text comes down line by line while
+    // they are few, else as the whole text in one copy; the host's records go up one copy per run of neighbours
+    uint64_t n_special = 0;
+    for (uint64_t i = 0; i < n; ++i) n_special += mark[i] || warn[i];
+    if (n_special) {
+        std::vector<uint64_t> lo(n + 1), ro(n + 1);
+        if (oge_memcpy(cc.ctx, lo.data(), dlo.as<void>(), (n + 1) * 8, 2) || oge_memcpy(cc.ctx, ro.data(), dro.as<void>(), (n + 1) * 8, 2))
+            return cc.fail("device->host copy");
+        const bool whole = n_special > 4096;
+        bytevec text;
+        if (whole) {
+            text.resize(bytes);
+            if (oge_memcpy(cc.ctx, text.data(), d_text, bytes, 2)) return cc.fail("device->host copy");
+        }
+        std::string one;
+        std::vector<uint8_t> run, rec;  // the records of consecutive marked lines, back to back
+        uint64_t run_at = 0;
+        auto flush = [&]() -> int {
+            const int rc = run.empty() ? 0 : oge_memcpy(cc.ctx, drecs.as<uint8_t>() + run_at, run.data(), run.size(), 1);
+            run.clear();
+            return rc;
+        };
+        for (uint64_t i = 0; i < n; ++i) {
+            if (!mark[i] && !warn[i]) continue;
+            const uint64_t len = lo[i + 1] - 1 - lo[i];
+            const char *line = whole ? (const char *)text.data() + lo[i] : nullptr;
+            if (!whole) {
+                one.resize(len);
+                if (len && oge_memcpy(cc.ctx, &one[0], d_text + lo[i], len, 2)) return cc.fail("device->host copy");
+                line = one.data();
+            }
+            if (warn[i]) warn_rnext(line, len);
+            if (!mark[i]) continue;
+            uint64_t got = 0;
+            rec.resize(ro[i + 1] - ro[i]);
+            if (oge_sam_host_record(line, len, &so.o, rec.data(), rec.size(), &got) || got != rec.size()) {
+                uint64_t hdr_lines = 0;
+                oge_sam_header(head.data(), hl, &hl, &hdr_lines);
+                fprintf(stderr, "openge: error reading %s: line %llu: %s\n", name.c_str(), (unsigned long long)(hdr_lines + i + 1),
+                        oge_last_error(nullptr));
+                return -1;
+            }
+            if (!run.empty() && run_at + run.size() != ro[i] && flush()) return cc.fail("host->device copy");
+            if (run.empty()) run_at = ro[i];
+            run.insert(run.end(), rec.begin(), rec.end());
+            if (run.size() > (64u << 20) && flush()) return cc.fail("host->device copy");
+        }
+        if (flush()) return cc.fail("host->device copy");
+    }
+    if (ref_lens) *ref_lens = f.ref_lens;
+    b.header = f.header;
+    b.ref_names = f.ref_names;
+    b.n = n;
+    b.d_recs = (uint8_t *)drecs.release();
+    b.d_offs = (uint64_t *)dro.release();
+    b.d_bytes = total;
+    b.dev_valid = true;
+    b.host_valid = false;
+    if (AlgorithmModule::isVerbose()) {
+        double te = 0;
+        oge_ctx_timing(cc.ctx, "sam_emit", &te);
+        fprintf(stderr, "[openge] SAM input: %llu lines, %llu text bytes -> %llu record bytes, %llu lines built on the host, emit %.3f ms\n",
+                (unsigned long long)n, (unsigned long long)bytes, (unsigned long long)total, (unsigned long long)n_host, te);
+    }
+    return 0;
+}
+
+// One SAM file into HBM (the streamed loader, else a host read and one copy up) and its records.
+static int read_sam_device(ChainContext &cc, const std::string &path, bool need_sort_room, ReadBatch &b, std::vector<int32_t> *ref_lens = nullptr) {
+    LoadedFile z(cc.ctx);
+    if (file_to_device(cc, path, LOAD_STREAM, z) != 0) {
+        bytevec text;
+        std::string err;
+        if (!read_file_bytes(path, text, cc.threads > 0 ? cc.threads : 8, err)) {
+            fprintf(stderr, "openge: error reading %s: %s\n", path.c_str(), err.c_str());
+            return -1;
+        }
+        if (z.buf.alloc(text.size() + 16) || oge_memcpy(cc.ctx, z.buf.as<void>(), text.data(), text.size(), 1)) {
+            fprintf(stderr, "openge: error reading %s: the SAM text (%llu bytes) does not fit in device memory; SAM input larger than HBM is not "
+                    "provided\n", path.c_str(), (unsigned long long)text.size());
+            return -1;
+        }
+        z.zbytes = text.size();
+    }
+    return sam_device_records(cc, path, z.buf.as<uint8_t>(), z.zbytes, need_sort_room, b, ref_lens);
+}
+
 // ----------------------------------------------------------------------------------- FileReader
 int FileReader::read_device(ChainContext &cc, ReadBatch &b, const std::string &path) {
     const auto t0 = clk();
@@ -413,18 +623,22 @@ int FileReader::runInternal(ChainContext &cc, ReadBatch &b) {
     if (files_.empty()) files_.push_back("stdin");
     std::vector<uint64_t> file_end;  // record count after each file
     const char *rd = getenv("OGE_READER");
+    // one SAM file (first byte '@'): its text into HBM and parsed there; with --gpus on rank 0, then run_ranks'
+    // unsharded distribution
+    const bool one_sam = files_.size() == 1 && files_[0] != "stdin" && files_[0] != "-" && file_is_sam(files_[0]);
+    if (one_sam && !(rd && std::string(rd) == "host")) return read_sam_device(cc, files_[0], sink_sorts(), b);
     // the byte-range sharded reader by default only over the host-staged transport, where every multi-rank
     // test ran; over RCCL (an 8-GPU node) it is opt-in (OGE_READER=sharded) until a G > 1 RCCL run of it has
     // been recorded: its rank joins and tail fetch are collectives that a fall-back cannot undo
     const bool want_shards = cc.gpus > 1 && files_.size() == 1 && files_[0] != "stdin" && files_[0] != "-" && sink_takes_shards() &&
-                             !(rd && (std::string(rd) == "host" || std::string(rd) == "whole"));
+                             !one_sam && !(rd && (std::string(rd) == "host" || std::string(rd) == "whole"));
     if (want_shards && cc.init_ranks()) return -1;  // the ranks (and so the transport) are needed here anyway
     const bool rccl = !cc.comms.empty() && cc.comms[0] && std::string(oge_comm_transport(cc.comms[0])) == "rccl";
     if (want_shards && (!rccl || (rd && std::string(rd) == "sharded"))) {
         const int r = read_sharded(cc, b, files_[0]);
         if (r <= 0) return r;  // 1: the host reader reports why the file cannot be read
     }
-    if (files_.size() == 1 && files_[0] != "stdin" && files_[0] != "-" && !(rd && std::string(rd) == "host")) {
+    if (files_.size() == 1 && files_[0] != "stdin" && files_[0] != "-" && !one_sam && !(rd && std::string(rd) == "host")) {
         const int r = read_device(cc, b, files_[0]);
         if (r <= 0) return r;  // 1: fall through to the host reader (it reports format errors)
     }
@@ -433,7 +647,21 @@ int FileReader::runInternal(ChainContext &cc, ReadBatch &b) {
         const std::string path = files_[i] == "stdin" ? "/dev/stdin" : files_[i];
         BamFile f;
         std::string err;
-        if (!bam_read_file(path, f, cc.threads > 0 ? cc.threads : 8, err)) {
+        const int threads = cc.threads > 0 ? cc.threads : 8;
+        const bool is_stdin = path == "/dev/stdin" || path == "-";
+        if (is_stdin || file_is_sam(path)) {  // a pipe cannot be looked at first: read it, then decide by its first byte
+            bytevec raw, stream;
+            bool ok = read_file_bytes(is_stdin ? "stdin" : path, raw, threads, err);
+            if (ok && !raw.empty() && raw[0] == '@') {
+                if (sam_host_file(cc, files_[i], raw, f)) return -1;
+            } else {
+                ok = ok && bgzf_inflate_all(raw.data(), raw.size(), stream, threads, err) && bam_parse(std::move(stream), f, err, threads);
+            }
+            if (!ok) {
+                fprintf(stderr, "openge: error reading %s: %s\n", files_[i].c_str(), err.c_str());
+                return -1;
+            }
+        } else if (!bam_read_file(path, f, threads, err)) {
             fprintf(stderr, "openge: error reading %s: %s\n", files_[i].c_str(), err.c_str());
             return -1;
         }
@@ -1393,6 +1621,11 @@ static int load_whole(ChainContext &cc, const std::string &path, const char *wha
 }
 
 int index_bam_file(ChainContext &cc, const std::string &path, const std::string &out) {
+    if (file_is_sam(path)) {
+        fprintf(stderr, "openge index: %s is SAM text; only a coordinate-sorted BAM file can be indexed (openge sort %s -o sorted.bam --index)\n",
+                path.c_str(), path.c_str());
+        return -1;
+    }
     LoadedFile z(cc.ctx);
     if (load_whole(cc, path, "index", false, z)) return -1;
     const uint8_t *d_bai = nullptr;
@@ -1428,6 +1661,53 @@ void report_stages(ChainContext &cc, const char *reduce, double t_format) {
     fprintf(stderr, "[openge] device: framing %.1f ms, inflate %.1f ms, record walk %.1f ms, %s %.1f ms; format %.3f s\n", ix, inf, walk,
             reduce, red, t_format);
 }
+
+// The one loader of stats / count / coverage: the input in HBM for either format, and the three reductions over
+// it.  A BAM file stays as its compressed bytes and takes the whole-file calls it always took (oge_bam_*_dev:
+// inflate, record walk and reduction under one hold, with their stage times for -v); a SAM file becomes records
+// in HBM (read_sam_device) and takes oge_stats_dev / oge_coverage_dev, with the contigs of its header text in the
+// place of the BAM file's binary reference list.  Everything is freed on every return.
+struct QcInput {
+    ChainContext &cc;
+    LoadedFile z;
+    ReadBatch b;
+    bool sam = false;
+    std::vector<int32_t> sam_lens;
+    std::string sam_names;
+    explicit QcInput(ChainContext &c) : cc(c), z(c.ctx) {}
+    ~QcInput() { cc.free_device(b); }
+    int load(const std::string &path) {
+        sam = file_is_sam(path);
+        return sam ? read_sam_device(cc, path, false, b, &sam_lens) : load_whole(cc, path, "upload", true, z);
+    }
+    int stats(uint32_t want, oge_bam_stats *s, const uint32_t **d_len, const uint64_t **d_cnt) {
+        return sam ? oge_stats_dev(cc.ctx, b.d_recs, b.d_offs, b.n, want, s, d_len, d_cnt)
+                   : oge_bam_stats_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, want, s, d_len, d_cnt);
+    }
+    int count(uint64_t *n) {  // a SAM file's lines have all been checked by now: the count is of records
+        if (sam) return *n = b.n, 0;
+        return oge_bam_count_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, n);
+    }
+    int coverage(int32_t binsize, const uint32_t **d_bins, uint64_t *nb, uint64_t *skipped, int32_t *overflow, int32_t *n_ref, const char **names,
+                 const int32_t **lens) {
+        if (!sam) {
+            uint64_t names_bytes = 0;
+            int rc = oge_bam_coverage_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, binsize, d_bins, nb, skipped, overflow);
+            z.buf.reset();
+            if (!rc) rc = oge_ctx_last_refs(cc.ctx, n_ref, names, &names_bytes, lens);
+            return rc;
+        }
+        for (auto &nm : b.ref_names) sam_names.append(nm.c_str(), nm.size() + 1);
+        *n_ref = (int32_t)sam_lens.size();
+        *names = sam_names.data();
+        *lens = sam_lens.data();
+        std::vector<uint64_t> base((size_t)*n_ref + 1);
+        int rc = oge_coverage_dev(cc.ctx, b.d_recs, b.d_offs, b.n, *n_ref, *lens, binsize, d_bins, skipped, overflow);
+        if (!rc) rc = oge_coverage_layout(*n_ref, *lens, binsize, base.data());
+        *nb = base[*n_ref];
+        return rc;
+    }
+};
 
 float pct(uint64_t a, uint64_t b) { return ((float)a / (float)b) * 100; }  // statistics.cpp:158: float32
 
@@ -1469,22 +1749,22 @@ struct TsvWriter {
 }  // namespace
 
 int stats_bam_file(ChainContext &cc, const std::string &path, bool inserts, bool lengths) {
-    LoadedFile z(cc.ctx);
-    if (load_whole(cc, path, "upload", true, z)) return -1;
+    QcInput in(cc);
+    if (in.load(path)) return -1;
     oge_bam_stats s;
     const uint32_t *d_len = nullptr;
     const uint64_t *d_cnt = nullptr;
     std::vector<uint32_t> len;
     std::vector<uint64_t> cnt;
-    int rc = oge_bam_stats_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, (inserts ? OGE_STATS_INSERTS : 0) | (lengths ? OGE_STATS_LENGTHS : 0), &s,
-                               &d_len, &d_cnt);
+    const uint32_t want = (inserts ? OGE_STATS_INSERTS : 0) | (lengths ? OGE_STATS_LENGTHS : 0);
+    int rc = in.stats(want, &s, &d_len, &d_cnt);
     if (!rc && lengths && s.n_lengths) {
         len.resize(s.n_lengths);
         cnt.resize(s.n_lengths);
         rc = oge_memcpy(cc.ctx, len.data(), d_len, s.n_lengths * 4, 2);
         if (!rc) rc = oge_memcpy(cc.ctx, cnt.data(), d_cnt, s.n_lengths * 8, 2);
     }
-    z.buf.reset();
+    in.z.buf.reset();
     if (rc) return cc.fail("stats");
     const auto t0 = clk();
     auto line = [](const char *label, uint64_t v, uint64_t of) {
@@ -1531,10 +1811,10 @@ int stats_bam_file(ChainContext &cc, const std::string &path, bool inserts, bool
 }
 
 int count_bam_file(ChainContext &cc, const std::string &path) {
-    LoadedFile z(cc.ctx);
+    QcInput in(cc);
     uint64_t n = 0;
-    if (load_whole(cc, path, "upload", true, z)) return -1;
-    if (oge_bam_count_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, &n)) return cc.fail("count");
+    if (in.load(path)) return -1;
+    if (in.count(&n)) return cc.fail("count");
     printf("%llu\n", (unsigned long long)n);
     if (fflush(stdout) != 0 || ferror(stdout)) {
         fprintf(stderr, "openge: error writing to stdout\n");
@@ -1544,18 +1824,15 @@ int count_bam_file(ChainContext &cc, const std::string &path) {
 }
 
 int coverage_bam_file(ChainContext &cc, const std::string &path, const std::string &out, int binsize, bool omit_uncovered) {
-    LoadedFile z(cc.ctx);
+    QcInput in(cc);
     uint64_t nb = 0, skipped = 0;
-    if (load_whole(cc, path, "upload", true, z)) return -1;
+    if (in.load(path)) return -1;
     const uint32_t *d_bins = nullptr;
     int32_t overflow = 0, n_ref = 0;
     const char *names = nullptr;
     const int32_t *lens = nullptr;
-    uint64_t names_bytes = 0;
     std::vector<uint32_t> bins;
-    int rc = oge_bam_coverage_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, binsize, &d_bins, &nb, &skipped, &overflow);
-    z.buf.reset();
-    if (!rc) rc = oge_ctx_last_refs(cc.ctx, &n_ref, &names, &names_bytes, &lens);
+    int rc = in.coverage(binsize, &d_bins, &nb, &skipped, &overflow, &n_ref, &names, &lens);
     if (!rc && nb) {
         bins.resize(nb);
         rc = oge_memcpy(cc.ctx, bins.data(), d_bins, nb * 4, 2);

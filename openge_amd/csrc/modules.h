@@ -99,7 +99,10 @@ protected:
     friend class ReadSorter;
 };
 
-// FileReader (algorithms/file_reader.cpp:29-63): BAM input(s).  Several inputs are interleaved as
+// FileReader (algorithms/file_reader.cpp:29-63): BAM and SAM input(s); an input whose first byte is '@' is SAM
+// text (util/read_stream_reader.h:45-85) and is parsed into records on the GPU: one SAM file as text in HBM
+// (oge_sam_lines_dev / _size_dev / _emit_dev, the records stay there), several inputs, a SAM file among BAM
+// files and stdin through oge_sam_parse on the host path.  Several inputs are interleaved as
 // the reference's MultiReader does (a ByPosition merge of the file heads,
 // util/read_stream_reader.h:132-153) unless a ReadSorter follows, which makes the interleaving
 // irrelevant; the header is the first file's (a differing dictionary only warns, :116-124).

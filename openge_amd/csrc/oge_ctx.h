@@ -70,6 +70,14 @@ struct oge_ctx {
     std::string text_names;
     std::vector<uint32_t> text_name_off;
     const void *text_names_ptr = nullptr, *text_name_off_ptr = nullptr;
+    // the contig table the last oge_sam_* call uploaded (workspaces "sam_names" / "sam_name_off" / "sam_slots"),
+    // and what the last oge_sam_parse call returned (host memory, valid until the next one)
+    bool sam_names_valid = false;
+    std::string sam_names;
+    std::vector<uint32_t> sam_name_off;
+    const void *sam_names_ptr = nullptr, *sam_name_off_ptr = nullptr, *sam_slots_ptr = nullptr;
+    std::vector<uint8_t> sam_out_recs, sam_out_warn;
+    std::vector<uint64_t> sam_out_off;
     std::map<std::string, uint64_t> counters;  // per call: work counts a stage reports (oge_ctx_counter)
     bool last_scan_generic = false;  // realign scan fell back to the byte-wise kernel
     double scan_t[3] = {0, 0, 0};    // realign scan host timings: validate, upload, device + download

@@ -16,6 +16,13 @@
 // --nosplit/--nothreads: K = min(12, threads / 2), command_dedup.cpp:46-48).  Sort by name (-b)
 // gives the true name order (the reference merges name-sorted temp runs by position,
 // util/read_stream_reader.h:94-97, so its output is name-sorted only within one run of -n reads).
+// SAM input: every input whose first byte is '@' is SAM text (util/read_stream_reader.h:45-85), parsed into BAM
+// records on the GPU (csrc/sam_parse.hip; FileReader, and stats / count / coverage); one SAM file goes into HBM as
+// text and its records stay there, several inputs, a SAM file among BAM files and stdin are read on the host and
+// parsed through oge_sam_parse.  `index` refuses SAM; a SAM text larger than HBM is refused, not spilled.  Where the
+// reference's reader aborts or corrupts (QUAL or SEQ `*`, lowercase bases, B and H tags, integers past int32, a
+// last line without its newline) the SAM specification is followed; a line that does not parse ends the command
+// with its line number before anything is written.
 // -F sam|fastq|bam: SAM text from view, mergesort, sort and dedup, FASTQ text from view to stdout, both
 // formatted on the GPU (FileWriter::write_text).  FASTQ files (the reference's _1.fastq / _2.fastq / .fastq
 // split), text output with --gpus or --index, the RAWBAM and CRAM formats and -F on localrealign fail loudly
@@ -121,7 +128,9 @@ bool parse(int argc, const char **argv, const std::vector<Opt> &opts, Parsed &p)
 void usage_top() {
     fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, view, index, stats, count, coverage,\n"
                     "          version\n"
-                    "\n    openge view [-o out] [-n N] [-q MAPQ] [-l LEN] [-r REGION] [-B N] [-E N] in.bam\n"
+                    "\n    Inputs are BAM files or SAM text (first byte '@'; also on stdin, and mixed with BAM files); SAM is parsed\n"
+                    "    on the GPU.  index takes BAM only.\n"
+                    "\n    openge view [-o out] [-n N] [-q MAPQ] [-l LEN] [-r REGION] [-B N] [-E N] in.bam|in.sam\n"
                     "                                        the reads that pass the filters (-l: 64, 64-72, -64 or +64), as SAM\n"
                     "                                        on stdout, else in the format of -F or of the output name's suffix;\n"
                     "                                        -B / -E trim bases from the read ends, FASTQ only\n"
@@ -130,9 +139,9 @@ void usage_top() {
                     "                                        or --index)\n"
                     "    openge index in.bam [-o out.bai]    BAM index of a coordinate-sorted file (default in.bam.bai)\n"
                     "    mergesort / sort / dedup --index    also write <out>.bai (one GPU, file output, coordinate order)\n"
-                    "    openge stats [-I] [-L] in.bam       flag counts, Sorted: Yes/No, insert sizes (-I), read lengths (-L)\n"
-                    "    openge count in.bam                 the number of reads\n"
-                    "    openge coverage [-o out.tsv] [-b N] [--omituncoveredbases] in.bam\n"
+                    "    openge stats [-I] [-L] in.bam|in.sam  flag counts, Sorted: Yes/No, insert sizes (-I), read lengths (-L)\n"
+                    "    openge count in.bam|in.sam          the number of reads\n"
+                    "    openge coverage [-o out.tsv] [-b N] [--omituncoveredbases] in.bam|in.sam\n"
                     "                                        depth per bin of N bases (default 100); one file, one GPU\n"
                     "\nGPU options (every command):\n"
                     "    --device N              first GPU\n"

@@ -321,6 +321,12 @@ def lib() -> C.CDLL:
         "oge_text_emit_dev": (C.c_int, [vp, vp, vp, vp, u64, u64, vp, vp, u64]),
         "oge_text_host_line": (C.c_int, [vp, u64, vp, vp, u64, C.POINTER(u64)]),
         "oge_text_format": (C.c_int, [vp, vp, u64, vp, u64, vp, vp, u64, C.POINTER(u64)]),
+        "oge_sam_header": (C.c_int, [vp, u64, C.POINTER(u64), C.POINTER(u64)]),
+        "oge_sam_lines_dev": (C.c_int, [vp, vp, u64, u64, vp, u64, C.POINTER(u64)]),
+        "oge_sam_size_dev": (C.c_int, [vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]),
+        "oge_sam_emit_dev": (C.c_int, [vp, vp, vp, vp, u64, u64, vp, vp, u64]),
+        "oge_sam_host_record": (C.c_int, [vp, u64, vp, vp, u64, C.POINTER(u64)]),
+        "oge_sam_parse": (C.c_int, [vp, vp, u64, C.POINTER(u64), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp)]),
         "oge_mergesort_opts_init": (None, [vp]),
         "oge_mergesort_bgzf_dev": (C.c_int, [vp, vp, u64, vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64),
                                              C.POINTER(u64)]),
@@ -729,6 +735,50 @@ class Context:
         buf = C.create_string_buffer(16 + 12 * len(rec) + 256 * 2)
         check(lib().oge_text_host_line(rec, len(rec), C.byref(opts), buf, len(buf), C.byref(nb)))
         return buf.raw[:nb.value]
+
+    # ---- SAM input (csrc/sam_parse.hip)
+    @staticmethod
+    def sam_header(text: bytes) -> tuple[int, int]:
+        """oge_sam_header: (the bytes, the lines) of the leading '@' lines."""
+        hl, nl = C.c_uint64(), C.c_uint64()
+        check(lib().oge_sam_header(text, len(text), C.byref(hl), C.byref(nl)))
+        return hl.value, nl.value
+
+    def sam_lines_dev(self, d_text, nbytes: int, body_off: int, d_line_off=None, cap: int = 0) -> int:
+        """oge_sam_lines_dev: the line count; with d_line_off (cap entries) also the line table."""
+        n = C.c_uint64()
+        check(lib().oge_sam_lines_dev(self.h, d_text, nbytes, body_off, d_line_off, cap, C.byref(n)), self.h)
+        return n.value
+
+    def sam_size_dev(self, d_text, d_line_off, n: int, opts: TextOpts, d_rec_off, d_host_mark, d_warn) -> tuple[int, int]:
+        """oge_sam_size_dev: fills d_rec_off (n + 1 u64), d_host_mark and d_warn (n u8) -> (record bytes, host lines)."""
+        total, n_host = C.c_uint64(), C.c_uint64()
+        check(lib().oge_sam_size_dev(self.h, d_text, d_line_off, n, C.byref(opts), d_rec_off, d_host_mark, d_warn, C.byref(total),
+                                     C.byref(n_host)), self.h)
+        return total.value, n_host.value
+
+    def sam_emit_dev(self, d_text, d_line_off, d_rec_off, first: int, count: int, opts: TextOpts, d_recs, cap: int) -> None:
+        """oge_sam_emit_dev: the records of lines [first, first + count) at d_recs."""
+        check(lib().oge_sam_emit_dev(self.h, d_text, d_line_off, d_rec_off, first, count, C.byref(opts), d_recs, cap), self.h)
+
+    @staticmethod
+    def sam_host_record(line: bytes, opts: TextOpts) -> bytes:
+        """oge_sam_host_record: one line's record built on the host."""
+        nb = C.c_uint64()
+        buf = C.create_string_buffer(64 + 4 * len(line))
+        check(lib().oge_sam_host_record(line, len(line), C.byref(opts), buf, len(buf), C.byref(nb)))
+        return buf.raw[:nb.value]
+
+    def sam_parse(self, text: bytes) -> tuple[int, np.ndarray, np.ndarray, np.ndarray]:
+        """oge_sam_parse: (header bytes, records u8 with 16 bytes of slack, offsets u64[n + 1], warning bytes u8[n])."""
+        hl, nb, n = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        recs, offs, warn = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().oge_sam_parse(self.h, text, len(text), C.byref(hl), C.byref(recs), C.byref(nb), C.byref(offs), C.byref(n), C.byref(warn)),
+              self.h)
+
+        def copy(p, count, ty):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ty)), (count,)).copy() if count else np.zeros(0, ty)
+        return hl.value, copy(recs, nb.value + 16, C.c_uint8), copy(offs, n.value + 1, C.c_uint64), copy(warn, n.value, C.c_uint8)
 
     @staticmethod
     def coverage_layout(ref_len, binsize: int) -> np.ndarray:
