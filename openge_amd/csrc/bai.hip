@@ -469,12 +469,7 @@ int oge_bai_build_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_of
     if (n_ref < 0) return oge_fail(ctx, OGE_ERR_LIMIT, "index: n_ref < 0");
     if (n >= 0xFFFFFFFFull) return oge_fail(ctx, OGE_ERR_LIMIT, "index: more than 2^32-2 records");
     if (n && (!d_recs || !d_off || !d_uoff || !d_cstart)) return oge_fail(ctx, OGE_ERR_ARG, "index: null argument");
-    OgeStageTimer *tm = ctx->begin_stage("bai_build");
-    struct EndStage {
-        oge_ctx *c;
-        OgeStageTimer *t;
-        ~EndStage() { c->end_stage(t); }
-    } es{ctx, tm};
+    OgeStage stage(ctx, "bai_build");
     Scratch scratch{ctx};  // destroyed first: the stage's stop event follows the frees' synchronisation
     hipStream_t st = ctx->stream;
     const uint64_t nr1 = (uint64_t)n_ref + 1;
@@ -610,8 +605,7 @@ int oge_bai_build_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off
                       const uint64_t *d_uoff, const uint64_t *d_cstart, uint64_t nblk, const uint8_t **d_bai, uint64_t *bai_bytes) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!d_bai || !bai_bytes) return oge_fail(ctx, OGE_ERR_ARG, "oge_bai_build_dev: null argument");
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     *d_bai = nullptr;
     *bai_bytes = 0;
     return oge_bai_build_impl(ctx, d_recs, d_off, n, n_ref, stream_base, d_uoff, d_cstart, nblk, d_bai, bai_bytes);

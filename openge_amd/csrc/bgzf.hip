@@ -1617,8 +1617,7 @@ extern "C" int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t
     // the context's search (oge_ctx_set_deflate_search); level 0 writes stored blocks whatever the parse finds
     const int search = level == 0 ? OGE_DEFL_FAST : ctx->deflate_search;
     if (dst_cap < oge_bgzf_bound(n)) return oge_fail(ctx, OGE_ERR_ARG, "dst_cap < oge_bgzf_bound(n)");
-    hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     *out_bytes = 0;
     if (!n) return OGE_OK;
     const uint64_t nblk = (n + kPay - 1) / kPay;
@@ -1691,7 +1690,7 @@ extern "C" int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t
     }();
     OGE_HIP_TRY(ctx, hipMemcpyAsync(zpow, &zh, sizeof(zh), hipMemcpyHostToDevice, ctx->stream));
     OGE_HIP_TRY(ctx, hipMemsetAsync(base, 0, 8, ctx->stream));
-    OgeStageTimer *tm = ctx->begin_stage("bgzf_deflate");
+    OgeStage stage(ctx, "bgzf_deflate");
     hipEvent_t ev[4];
     for (auto &e : ev) OGE_HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     struct Evs {
@@ -1740,7 +1739,7 @@ extern "C" int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t
             OGE_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ev[s], 0));
         }
     }
-    ctx->end_stage(tm);
+    stage.end();
     uint64_t total = 0;
     OGE_HIP_TRY(ctx, hipMemcpyAsync(&total, base, 8, hipMemcpyDeviceToHost, ctx->stream));
     OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

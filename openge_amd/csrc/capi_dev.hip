@@ -6,6 +6,7 @@
 #include "synth.h"
 #include "records.h"
 #include "markdup_stages.h"
+#include "sam_parse.h"
 
 #include <cstdio>
 #include <cstring>
@@ -121,22 +122,29 @@ void *oge_ctx::scratch(const char *name, size_t bytes) {
     return ws(name, bytes);
 }
 
-OgeStageTimer *oge_ctx::begin_stage(const char *name) {
-    if (!timing) return nullptr;
-    if (event_pool_used == event_pool.size()) {
+void OgeStage::begin(const char *name) {
+    end();
+    if (!ctx->timing) return;
+    if (ctx->event_pool_used == ctx->event_pool.size()) {
         OgeStageTimer t;
         hipEventCreate(&t.start);
         hipEventCreate(&t.stop);
-        event_pool.push_back(t);
+        ctx->event_pool.push_back(t);
     }
-    OgeStageTimer *t = &event_pool[event_pool_used++];
-    hipEventRecord(t->start, stream);
-    stage_events[name].push_back(*t);
-    return t;
+    open = &ctx->event_pool[ctx->event_pool_used++];
+    hipEventRecord(open->start, ctx->stream);
+    ctx->stage_events[name].push_back(*open);
 }
 
-void oge_ctx::end_stage(OgeStageTimer *t) {
-    if (t) hipEventRecord(t->stop, stream);
+void OgeStage::end() {
+    if (open) hipEventRecord(open->stop, ctx->stream);
+    open = nullptr;
+}
+
+OgeCall::OgeCall(oge_ctx *c, bool hold) : ctx(c), held(hold ? 1 : 0) {
+    (void)hipSetDevice(ctx->device);
+    ctx->reset_timing();
+    ctx->timing_hold += held;
 }
 
 void oge_ctx::reset_timing() {
@@ -147,6 +155,45 @@ void oge_ctx::reset_timing() {
     stage_events.clear();
     counters.clear();
     event_pool_used = 0;
+}
+
+int oge_contig_table(oge_ctx *ctx, OgeContigTable *tab, const oge_text_opts *o, const char *who) {
+    const std::string w(who);
+    if (!o) return oge_fail(ctx, OGE_ERR_ARG, (w + ": null argument").c_str());
+    if (o->n_ref < 0 || (o->n_ref && (!o->ref_names || !o->ref_name_off)))
+        return oge_fail(ctx, OGE_ERR_ARG, (w + ": n_ref < 0 or no contig names").c_str());
+    for (int32_t r = 0; r < o->n_ref; ++r)
+        if (o->ref_name_off[r + 1] < o->ref_name_off[r]) return oge_fail(ctx, OGE_ERR_ARG, (w + ": contig name offsets decrease").c_str());
+    if (!tab) return OGE_OK;
+    const uint32_t bytes = o->n_ref ? o->ref_name_off[o->n_ref] : 0;
+    std::vector<uint32_t> offs(o->ref_name_off ? o->ref_name_off : nullptr, o->ref_name_off ? o->ref_name_off + o->n_ref + 1 : nullptr);
+    if (offs.empty()) offs.push_back(0);
+    const uint32_t slots = tab->ws_slots ? oge_sam_table_slots(o->n_ref) : 0;
+    uint8_t *d_names = (uint8_t *)ctx->ws(tab->ws_names, (size_t)bytes + 8);
+    uint32_t *d_name_off = (uint32_t *)ctx->ws(tab->ws_name_off, offs.size() * 4);
+    uint32_t *d_slots = tab->ws_slots ? (uint32_t *)ctx->ws(tab->ws_slots, (size_t)slots * 4) : nullptr;
+    if (!d_names || !d_name_off || (tab->ws_slots && !d_slots)) return OGE_ERR_HIP;
+    tab->n_slots = slots;
+    if (tab->valid && tab->d_names == d_names && tab->d_name_off == d_name_off && tab->d_slots == d_slots && tab->name_off == offs &&
+        tab->names.size() == bytes && (!bytes || !memcmp(tab->names.data(), o->ref_names, bytes)))
+        return OGE_OK;
+    tab->valid = false;
+    tab->names.assign(bytes ? o->ref_names : "", bytes);
+    tab->name_off = offs;
+    std::vector<uint32_t> table(slots, 0);
+    if (d_slots) oge_sam_table_build(o->n_ref, (const uint8_t *)tab->names.data(), offs.data(), table.data());
+    std::string padded = tab->names;
+    padded.append(8, '\0');
+    OGE_HIP_TRY(ctx, hipMemcpyAsync(d_names, padded.data(), padded.size(), hipMemcpyHostToDevice, ctx->stream));
+    OGE_HIP_TRY(ctx, hipMemcpyAsync(d_name_off, offs.data(), offs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (d_slots) OGE_HIP_TRY(ctx, hipMemcpyAsync(d_slots, table.data(), table.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffers go out of scope
+    tab->d_names = d_names;
+    tab->d_name_off = d_name_off;
+    tab->d_slots = d_slots;
+    tab->valid = true;
+    ctx->counters[tab->counter] += 1;
+    return OGE_OK;
 }
 
 extern "C" {
@@ -334,8 +381,7 @@ int oge_memcpy(oge_ctx *ctx, void *dst, const void *src, uint64_t bytes, int kin
 // ---------------------------------------------------------------- sort
 int oge_sort_coord_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref, uint32_t *d_perm) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
-    hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     uint64_t *k;
     uint32_t *v;
     int rc = oge_sort_keys_dev(ctx, d_recs, d_off, n, n_ref, false, &k, &v);
@@ -347,8 +393,7 @@ int oge_sort_coord_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_of
 int oge_gather_records_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, const uint32_t *d_perm, uint64_t n,
                            uint8_t *d_out, uint64_t *d_out_off) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
-    hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     return oge_gather_with_sizes(ctx, d_recs, d_off, d_perm, nullptr, n, d_out, d_out_off, nullptr, nullptr);
 }
 
@@ -400,8 +445,7 @@ int oge_sort_name(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const u
 int oge_markdup_dev(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_markdup_opts *opts,
                     uint8_t *d_dup, int apply, uint64_t *n_dup_out) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
-    hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     uint64_t nd = 0;
     int rc = oge_markdup_run(ctx, d_recs, d_off, n, opts, d_dup, apply, &nd);
     if (n_dup_out) *n_dup_out = nd;
@@ -436,8 +480,7 @@ int oge_sort_markdup_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_
     //   5 record gather: sorted records written once with bin recomputed and 0x400 applied
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!opts) return oge_fail(ctx, OGE_ERR_ARG, "sort_markdup: opts is NULL");
-    hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     // d_out holds the records' byte total and is only written by the final gather: until then it is
     // the scratch arena of the pipeline (input summaries, mate-join and group buffers), which keeps
     // the 300M-read footprint at the two record arenas + ~30 GB
@@ -462,7 +505,7 @@ int oge_sort_markdup_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_
     unsigned int *counts = oge_sort_counts(ctx);
     if (!counts) return OGE_ERR_HIP;
     OGE_HIP_TRY(ctx, hipMemsetAsync(counts, 0, 32, ctx->stream));
-    OgeStageTimer *t = ctx->begin_stage("input_pass");
+    OgeStage stage(ctx, "input_pass");
     OgePassArgs a = {};
     a.recs = d_recs;
     a.off = d_off;
@@ -476,7 +519,7 @@ int oge_sort_markdup_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_
     a.keyred = (unsigned long long *)(counts + 4);
     rc = oge_input_pass(ctx, a);
     if (rc) return rc;
-    ctx->end_stage(t);
+    stage.end();
     uint64_t *k;
     uint32_t *v;
     RecMeta *meta = (RecMeta *)ctx->ws("md_meta", (n + 1) * sizeof(RecMeta));

@@ -189,8 +189,7 @@ extern "C" int oge_sort_markdup_chunked(oge_ctx *ctx, uint8_t *h_recs, const uin
     if (opts && opts->compat_nonverbose_index) return oge_fail(ctx, OGE_ERR_ARG, "chunked dedup: compat_nonverbose_index is not supported");
     if (opts && opts->n_ref != n_ref) return oge_fail(ctx, OGE_ERR_ARG, "oge_sort_markdup_chunked: opts->n_ref differs from n_ref");
     if (n > 0xFFFFFFFEull) return oge_fail(ctx, OGE_ERR_LIMIT, "chunked: more than 2^32-2 records");
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     if (n_dup) *n_dup = 0;
     const uint64_t total = n ? h_off[n] - h_off[0] : 0;
     // per-read bytes the dedup keeps for the whole input: summary 64, minimal record <= 64 (typical
@@ -213,7 +212,7 @@ extern "C" int oge_sort_markdup_chunked(oge_ctx *ctx, uint8_t *h_recs, const uin
     uint8_t *A = (uint8_t *)ctx->ws("chk_a", chunk_bytes + 64);
     uint8_t *B = (uint8_t *)ctx->ws("chk_b", chunk_bytes + 64);
     if (!A || !B) return OGE_ERR_HIP;
-    OgeStageTimer *t = ctx->begin_stage("chunk_runs");
+    OgeStage stage(ctx, "chunk_runs");
     for (uint64_t r0 = 0; r0 < n;) {
         uint64_t r1 = r0 + 1;
         while (r1 < n && h_off[r1 + 1] - h_off[r0] <= chunk_bytes) ++r1;
@@ -241,7 +240,7 @@ extern "C" int oge_sort_markdup_chunked(oge_ctx *ctx, uint8_t *h_recs, const uin
         runs.push_back(std::move(run));
         r0 = r1;
     }
-    ctx->end_stage(t);
+    stage.end();
     if (n_runs) *n_runs = runs.size();
 
     // ---- 2. key ranges that fit
@@ -256,7 +255,7 @@ extern "C" int oge_sort_markdup_chunked(oge_ctx *ctx, uint8_t *h_recs, const uin
     uint8_t *dup_all = nullptr;
     GrowBuf mrec{ctx};
     if (opts && n) {
-        t = ctx->begin_stage("chunk_dedup");
+        stage.begin("chunk_dedup");
         meta_all = (RecMeta *)ctx->ws("chk_meta", (n + 1) * sizeof(RecMeta));
         dup_all = (uint8_t *)ctx->ws("chk_dup", n + 1);
         if (!meta_all || !dup_all) return OGE_ERR_HIP;
@@ -322,11 +321,11 @@ extern "C" int oge_sort_markdup_chunked(oge_ctx *ctx, uint8_t *h_recs, const uin
         if ((rc = oge_md_pair_groups(ctx, opts, P, dup_all))) return rc;
         if ((rc = oge_md_frag_groups(ctx, F.fk, F.fv, n, dup_all))) return rc;
         OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->end_stage(t);
+        stage.end();
     }
 
     // ---- 4. output, range by range
-    t = ctx->begin_stage("chunk_output");
+    stage.begin("chunk_output");
     uint64_t gbase = 0, nd = 0;
     for (const Range &R : ranges) {
         uint64_t *d_off = (uint64_t *)ctx->ws("chk_off", (R.n + 1) * 8);
@@ -346,7 +345,7 @@ extern "C" int oge_sort_markdup_chunked(oge_ctx *ctx, uint8_t *h_recs, const uin
         if ((rc = cb(user, B, b_off, R.n))) return oge_fail(ctx, rc, "chunked: the output callback failed");
         gbase += R.n;
     }
-    ctx->end_stage(t);
+    stage.end();
     if (n_dup) *n_dup = nd;
     return OGE_OK;
 }

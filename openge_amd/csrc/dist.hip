@@ -613,7 +613,7 @@ static int dist_run(oge_comm *comm, const uint8_t *d_recs, const uint64_t *d_off
     if ((rc = D.agree(rc))) return rc;
 
     // ---- 1. range split
-    OgeStageTimer *t = ctx->begin_stage("dist_split");
+    OgeStage stage(ctx, "dist_split");
     uint64_t *keys = (uint64_t *)ctx->ws("dist_keys", (n + 1) * 8);
     uint64_t *samp = (uint64_t *)ctx->ws("dist_samp", oge_dist::kSamples * 8);
     if (!keys || !samp) rc = OGE_ERR_HIP;
@@ -645,7 +645,7 @@ static int dist_run(oge_comm *comm, const uint8_t *d_recs, const uint64_t *d_off
     if (!rc && n) rc = D.d2h(&total, d_off + n, 8);
     if (!rc && n) rc = D.d2h(&first, d_off, 8);
     if (!sort) {  // dedup: records stay where they are, in input order (record index = input position)
-        ctx->end_stage(t);
+        stage.end();
         if ((rc = D.agree(rc))) return rc;
         return dist_dedup(D, const_cast<uint8_t *>(d_recs), d_off, n, total - first, n_ref, d_spl, false, opts, d_out, d_out_off,
                           n_out, n_dup_total);
@@ -682,11 +682,11 @@ static int dist_run(oge_comm *comm, const uint8_t *d_recs, const uint64_t *d_off
         }
         for (int g = 0; g < G; ++g) bcnt[g] = bnd[g + 1] - bnd[g];
     }
-    ctx->end_stage(t);
+    stage.end();
     if ((rc = D.agree(rc))) return rc;
 
     // ---- 2. exchange + local sort
-    t = ctx->begin_stage("dist_exchange");
+    stage.begin("dist_exchange");
     oge_dist::Plan pr, pb;
     if ((rc = D.plan(cnt, &pr)) || (rc = D.plan(bcnt, &pb))) return rc;
     const uint64_t R = pr.rtot, RB = pb.rtot;
@@ -708,7 +708,7 @@ static int dist_run(oge_comm *comm, const uint8_t *d_recs, const uint64_t *d_off
         rc = hipGetLastError() == hipSuccess ? 0 : dist_hip_fail(ctx, __LINE__);
     }
     if (!rc) rc = oge_exclusive_scan_u64(ctx, roff, roff, R + 1);
-    ctx->end_stage(t);
+    stage.end();
     if ((rc = D.agree(rc))) return rc;
     if (R > 0xFFFFFFFEull) rc = oge_fail(ctx, OGE_ERR_LIMIT, "multi-GPU: more than 2^32-2 records on one rank after the exchange");
     uint8_t *out = (uint8_t *)ctx->ws("dist_out", RB + 64);
@@ -744,7 +744,7 @@ static int dist_dedup(Dist &D, uint8_t *rbuf, const uint64_t *roff, uint64_t R, 
     const int G = D.G;
     const uint32_t nspl = (uint32_t)G - 1;
     int rc = OGE_OK;
-    OgeStageTimer *t = nullptr;
+    OgeStage stage(ctx);
     uint8_t *out = (uint8_t *)ctx->ws("dist_out", RB + 64);
     uint64_t *out_off = (uint64_t *)ctx->ws("dist_out_off", (R + 1) * 8);
     if (!out || !out_off) rc = OGE_ERR_HIP;
@@ -782,7 +782,7 @@ static int dist_dedup(Dist &D, uint8_t *rbuf, const uint64_t *roff, uint64_t R, 
         // the context stream while the peers' parts move on a side stream (RCCL: queued there; the host
         // transport: its staged copies run there while this stream executes the pass), then the pass covers
         // the received records.  Every rank makes the exchange whatever happened before (agree() below).
-        t = ctx->begin_stage("input_pass");
+        stage.begin("input_pass");
         const int me = D.rank;
         const oge_dist::Plan &pb = *xr->pb, &pr = *xr->pr;
         hipStream_t side = ctx->side_stream(0);
@@ -809,11 +809,11 @@ static int dist_dedup(Dist &D, uint8_t *rbuf, const uint64_t *roff, uint64_t R, 
         if (side) (void)hipStreamSynchronize(side);  // the events may go: nothing is left on the side stream
         for (auto &e : ev)
             if (e) (void)hipEventDestroy(e);
-        ctx->end_stage(t);
+        stage.end();
     } else if (!rc) {
-        t = ctx->begin_stage("input_pass");
+        stage.begin("input_pass");
         pass(0, R);
-        ctx->end_stage(t);
+        stage.end();
     }
     if (sorted) {
         if (!rc) rc = oge_sort_keys_dev(ctx, rbuf, roff, R, n_ref, true, &k, &v, meta_in, meta);
@@ -845,7 +845,7 @@ static int dist_dedup(Dist &D, uint8_t *rbuf, const uint64_t *roff, uint64_t R, 
     if (!dup_pad || !dup || !desc || !desc0) rc = OGE_ERR_HIP;
     if (!rc) rc = hipMemsetAsync(dup_pad, 0, (size_t)G * stride, ctx->stream) == hipSuccess ? 0 : dist_hip_fail(ctx, __LINE__);
     OgeMdFrags F;
-    t = ctx->begin_stage("dist_frags");
+    stage.begin("dist_frags");
     if (!rc) rc = oge_md_cand_frag(ctx, opts, meta, R, true, &F);
     if (!rc && F.desc_ovf) rc = oge_fail(ctx, OGE_ERR_LIMIT, "multi-GPU dedup: a record offset exceeds 2^39");
     if (!rc && R) rc = hipMemcpyAsync(desc0, F.desc0, R * 8, hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess ? 0 : dist_hip_fail(ctx, __LINE__);
@@ -888,10 +888,10 @@ static int dist_dedup(Dist &D, uint8_t *rbuf, const uint64_t *roff, uint64_t R, 
         if (!rc) rc = oge_md_frag_groups(ctx, fkr, fvr, pf.rtot, dup_pad);
         if ((rc = D.agree(rc))) return rc;
     }
-    ctx->end_stage(t);
+    stage.end();
 
     // mate-join candidates -> owner of their RG:name hash, with their minimal records
-    t = ctx->begin_stage("dist_join");
+    stage.begin("dist_join");
     OgeMdPairs P;
     {
         uint64_t *cdk = (uint64_t *)ctx->ws("dist_cdk", (R + 1) * 8);
@@ -980,10 +980,10 @@ static int dist_dedup(Dist &D, uint8_t *rbuf, const uint64_t *roff, uint64_t R, 
         }
         if ((rc = D.agree(rc))) return rc;
     }
-    ctx->end_stage(t);
+    stage.end();
 
     // pair ReadEnds -> owner of their chunk-key hash
-    t = ctx->begin_stage("dist_pairs");
+    stage.begin("dist_pairs");
     {
         const uint32_t np = P.np;
         uint64_t *pdk = (uint64_t *)ctx->ws("dist_pdk", ((uint64_t)np + 1) * 8);
@@ -1022,16 +1022,16 @@ static int dist_dedup(Dist &D, uint8_t *rbuf, const uint64_t *roff, uint64_t R, 
         if (!rc) rc = oge_md_pair_groups(ctx, opts, Q, dup_pad);
         if ((rc = D.agree(rc))) return rc;
     }
-    ctx->end_stage(t);
+    stage.end();
 
     // ---- dup marks meet; 4. apply + gather
-    t = ctx->begin_stage("dist_reduce");
+    stage.begin("dist_reduce");
     rc = comm->reduce_scatter_max_u8("dup_marks", dup_pad, dup, stride);
-    ctx->end_stage(t);
-    t = ctx->begin_stage("md_apply");
+    stage.end();
+    stage.begin("md_apply");
     uint64_t nd = 0;
     if (!rc) rc = oge_md_apply_desc(ctx, desc0, R, dup, desc, &nd);
-    ctx->end_stage(t);
+    stage.end();
     if (!rc) rc = oge_gather_with_sizes(ctx, rbuf, roff, v, k, R, out, out_off, meta, dup, desc);
     if (!rc) rc = hipStreamSynchronize(ctx->stream) == hipSuccess ? 0 : dist_hip_fail(ctx, __LINE__);
     if ((rc = D.agree(rc))) return rc;
@@ -1286,9 +1286,8 @@ int oge_sort_markdup_dist(oge_comm *comm, const uint8_t *d_recs, const uint64_t 
     if (!comm || !d_out || !d_out_off || !n_out || (n && (!d_recs || !d_off)))
         return oge_fail(comm ? comm->ctx : nullptr, OGE_ERR_ARG, "oge_sort_markdup_dist: bad arguments");
     oge_ctx *ctx = comm->ctx;
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
-    if (!ctx->timing_hold) comm->clear_stats();  // a composite entry point (pipeline.hip) keeps its earlier exchanges
+    OgeCall call(ctx, /*hold=*/false);
+    if (!ctx->in_composite()) comm->clear_stats();  // a composite entry point (pipeline.hip) keeps its earlier exchanges
     if (opts && opts->n_ref != n_ref) return oge_fail(ctx, OGE_ERR_ARG, "oge_sort_markdup_dist: opts->n_ref differs from n_ref");
     return dist_run(comm, d_recs, d_off, n, n_ref, sort, opts, d_out, d_out_off, n_out, n_dup_total);
 }

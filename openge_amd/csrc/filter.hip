@@ -107,9 +107,9 @@ extern "C" int oge_filter_records_dev(oge_ctx *ctx, const uint8_t *d_recs, const
     }
     uint32_t *keep = (uint32_t *)ctx->ws("keep_flags", (n + 1) * 4);
     if (!keep) return OGE_ERR_HIP;
-    OgeStageTimer *t = ctx->begin_stage("filter");
+    OgeStage stage(ctx, "filter");
     k_keep_filter<<<oge_ceil_div(n, 256), 256, 0, ctx->stream>>>(d_recs, d_off, n, *o, keep);
     OGE_LAUNCH_CHECK(ctx);
-    ctx->end_stage(t);
+    stage.end();
     return compact_kept(ctx, d_recs, d_off, n, keep, o->count_limit, d_out, d_out_off, n_out);
 }

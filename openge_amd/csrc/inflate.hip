@@ -776,12 +776,11 @@ extern "C" int oge_bgzf_index_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zby
                                   uint64_t *d_uoff, uint32_t *d_crc, uint64_t cap, uint64_t *nblk) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!nblk || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
-    hipSetDevice(ctx->device);
-    ctx->reset_timing();
-    OgeStageTimer *tm = ctx->begin_stage("bgzf_index");
+    OgeCall call(ctx, /*hold=*/false);
+    OgeStage stage(ctx, "bgzf_index");
     OgeBgzfIndex ix;
     int rc = oge_bgzf_index_ws(ctx, d_z, zbytes, &ix);
-    ctx->end_stage(tm);
+    stage.end();
     if (rc == 1) {  // not an exact chain: the host walk (and its error messages)
         std::vector<uint8_t> h(zbytes);
         OGE_HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_z, zbytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -822,8 +821,7 @@ extern "C" int oge_bgzf_inflate_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t z
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (nblk && (!d_z || !d_d0 || !d_d1 || !d_uoff || !d_out)) return oge_fail(ctx, OGE_ERR_ARG, "null buffer");
     if ((uintptr_t)d_z & 3) return oge_fail(ctx, OGE_ERR_ARG, "d_z must be 4-byte aligned");
-    hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     if (!nblk) return OGE_OK;
     uint32_t *err = (uint32_t *)ctx->ws("infl_err", 16);
     // the 2^k zero-byte operators, then phase 2's per-lane combine operators (crc_zlane, 64-byte pieces)
@@ -841,9 +839,9 @@ extern "C" int oge_bgzf_inflate_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t z
     OGE_HIP_TRY(ctx, hipMemcpyAsync(err, init, 8, hipMemcpyHostToDevice, ctx->stream));
     OGE_HIP_TRY(ctx, hipMemcpyAsync(zpow, &zh, sizeof(zh), hipMemcpyHostToDevice, ctx->stream));
     // the lane decoder (inflate_lane.hip), CRC fused into its phase 2
-    OgeStageTimer *tm = ctx->begin_stage("bgzf_inflate");
+    OgeStage stage(ctx, "bgzf_inflate");
     const int rc = oge_inflate_lanes(ctx, d_z, zbytes, d_d0, d_d1, d_uoff, d_crc, nblk, d_out, err, zpow);
-    ctx->end_stage(tm);
+    stage.end();
     if (rc) return rc;
     uint32_t got[2];
     OGE_HIP_TRY(ctx, hipMemcpyAsync(got, err, 8, hipMemcpyDeviceToHost, ctx->stream));

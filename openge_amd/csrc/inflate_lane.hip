@@ -1721,22 +1721,23 @@ int oge_inflate_lanes(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const u
             ctx->infl_clean_next = known;
         }
         // each phase's own time (stages "infl_huff" / "infl_lz", summed over the chunks) on the one stream
+        OgeStage stage(ctx);
         if (use_prep) {
-            OgeStageTimer *t0 = S == 1 ? ctx->begin_stage("infl_prep") : nullptr;
+            if (S == 1) stage.begin("infl_prep");
             k_infl_prep<<<(uint32_t)((nb + 63) / 64), 64, 0, u.st>>>(d_z, zbytes, d0, d1, b0, nb, u.prep, u.pmeta, u.xtab);
             OGE_LAUNCH_CHECK(ctx);
-            ctx->end_stage(t0);
+            stage.end();
         }
-        OgeStageTimer *t1 = S == 1 ? ctx->begin_stage("infl_huff") : nullptr;
+        if (S == 1) stage.begin("infl_huff");
         k_infl_huff<<<g1, 64, 0, u.st>>>(d_z, zbytes, d0, d1, uoff, b0, nb, out, u.bitmap, u.xtab, u.scr, err, u.next, u.prep,
                                          u.pmeta);
         OGE_LAUNCH_CHECK(ctx);
-        ctx->end_stage(t1);
-        OgeStageTimer *t2 = S == 1 ? ctx->begin_stage("infl_lz") : nullptr;
+        stage.end();
+        if (S == 1) stage.begin("infl_lz");
         k_infl_lz<<<(uint32_t)std::min<uint64_t>(nb, (uint64_t)ncu), kT2, 0, u.st>>>(out, uoff, crc, u.bitmap, u.xtab, b0, nb,
                                                                                    zpow, err);
         OGE_LAUNCH_CHECK(ctx);
-        ctx->end_stage(t2);
+        stage.end();
         if (S == 1) ctx->infl_clean_ptr = u.bitmap, ctx->infl_clean_bytes = ctx->infl_clean_next;
     }
     if (S > 1) {  // the context stream waits for every chunk

@@ -1500,7 +1500,7 @@ int oge_md_frag_groups_win(oge_ctx *ctx, const oge_markdup_opts *opts, const Oge
     KeyLayout L;
     int rc = md_layout(ctx, opts, &L);
     if (rc) return rc;
-    OgeStageTimer *t = ctx->begin_stage("md_frag_win");  // nested in md_frags: shows which path ran
+    OgeStage stage(ctx, "md_frag_win");  // nested in md_frags: shows which path ran
     // the unmapped tail (refID' = n_ref) holds no fragment
     const int64_t amax = ((int64_t)opts->n_ref << 34) + (1ll << 32);
     WinPlan W;
@@ -1509,9 +1509,9 @@ int oge_md_frag_groups_win(oge_ctx *ctx, const oge_markdup_opts *opts, const Oge
     hipLaunchKernelGGL(k_frag_win, dim3(W.ntiles), dim3(kT), 0, ctx->stream, (const uint64_t *)f.fk, (const uint32_t *)f.fv,
                        f.skeys, n, L, (const uint2 *)W.bounds, cap, dup);
     OGE_LAUNCH_CHECK(ctx);
-    ctx->end_stage(t);
+    stage.end();
     if (W.novf) {  // the overflowing tiles' fragments through the sort-based stage
-        t = ctx->begin_stage("md_frag_ovf");
+        stage.begin("md_frag_ovf");
         uint64_t *ok = (uint64_t *)ctx->scratch("md_ofk", W.ovf_items * 8 + 8);
         uint32_t *ov = (uint32_t *)ctx->scratch("md_ofv", W.ovf_items * 4 + 4);
         unsigned int *cnt = (unsigned int *)ctx->ws("md_ocnt", 4);
@@ -1525,7 +1525,7 @@ int oge_md_frag_groups_win(oge_ctx *ctx, const oge_markdup_opts *opts, const Oge
         OGE_HIP_TRY(ctx, hipMemcpyAsync(&m, cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
         OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if ((rc = oge_md_frag_groups(ctx, ok, ov, m, dup))) return rc;
-        ctx->end_stage(t);
+        stage.end();
     }
     *done = true;
     return OGE_OK;
@@ -1540,16 +1540,16 @@ int oge_md_pair_groups_win(oge_ctx *ctx, const oge_markdup_opts *opts, const Oge
     KeyLayout L;
     int rc = md_layout(ctx, opts, &L);
     if (rc) return rc;
-    OgeStageTimer *t = ctx->begin_stage("md_pair_win");  // nested in md_pairs
+    OgeStage stage(ctx, "md_pair_win");  // nested in md_pairs
     WinPlan W;
     const uint32_t cap = md_win_cap(kPairCap);
     if ((rc = md_win_bounds(ctx, nullptr, P.pax, P.np, cap, P.dev, INT64_MAX, &W))) return rc;
     hipLaunchKernelGGL(k_pair_win, dim3(W.ntiles), dim3(kT), 0, ctx->stream, (const uint64_t *)P.hi, (const uint64_t *)P.lo,
                        (const uint2 *)P.idx, (const int64_t *)P.pax, (uint64_t)P.np, L, (const uint2 *)W.bounds, cap, dup);
     OGE_LAUNCH_CHECK(ctx);
-    ctx->end_stage(t);
+    stage.end();
     if (W.novf) {  // the overflowing tiles' pairs through the sort-based stage
-        t = ctx->begin_stage("md_pair_ovf");
+        stage.begin("md_pair_ovf");
         OgeMdPairs Q = P;
         if ((rc = pairs_hk(ctx, Q))) return rc;
         uint64_t *ok = (uint64_t *)ctx->scratch("md_ohk", W.ovf_items * 8 + 8);
@@ -1566,7 +1566,7 @@ int oge_md_pair_groups_win(oge_ctx *ctx, const oge_markdup_opts *opts, const Oge
         OGE_HIP_TRY(ctx, hipMemcpyAsync(&m, cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
         OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if ((rc = pair_groups_sorted(ctx, opts, ok, ov, m, P, dup))) return rc;
-        ctx->end_stage(t);
+        stage.end();
     }
     *done = true;
     return OGE_OK;
@@ -1637,7 +1637,7 @@ int oge_markdup_finish_pre(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off,
     const uint32_t nb = oge_ceil_div(n, kT);
 
     // ---- mate join ----
-    OgeStageTimer *t = ctx->begin_stage("md_matejoin");
+    OgeStage stage(ctx, "md_matejoin");
     OgeMdFrags F;
     if (pre) {  // the fused gather's products: only the scan / overflow read-back is left
         if (!pre->fused || pre->skeys != skeys || (d_desc && !pre->desc0))
@@ -1652,22 +1652,22 @@ int oge_markdup_finish_pre(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off,
     OgeMdPairs P;
     rc = oge_md_join_build(ctx, opts, d_recs, meta, n, F, &P);
     if (rc) return rc;
-    ctx->end_stage(t);
+    stage.end();
 
     // ---- pair groups ----
-    t = ctx->begin_stage("md_pairs");
+    stage.begin("md_pairs");
     bool done = false;
     rc = oge_md_pair_groups_win(ctx, opts, P, d_dup, &done);
     if (!rc && !done) rc = oge_md_pair_groups(ctx, opts, P, d_dup);
     if (rc) return rc;
-    ctx->end_stage(t);
+    stage.end();
 
     // ---- fragment groups ----
-    t = ctx->begin_stage("md_frags");
+    stage.begin("md_frags");
     rc = oge_md_frag_groups_win(ctx, opts, F, n, d_dup, &done);
     if (!rc && !done) rc = oge_md_frag_groups(ctx, F.fk, F.fv, n, d_dup);  // fk / fv were written by k_cand_frag
     if (rc) return rc;
-    ctx->end_stage(t);
+    stage.end();
 
     // ---- apply ----
     if (pre && pre->defer_apply && use_desc && !apply && !opts->compat_nonverbose_index) {
@@ -1676,7 +1676,7 @@ int oge_markdup_finish_pre(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off,
         *n_dup_out = ~0ull;
         return OGE_OK;
     }
-    t = ctx->begin_stage("md_apply");
+    stage.begin("md_apply");
     OGE_HIP_TRY(ctx, hipMemsetAsync(cnt, 0, 16, ctx->stream));
     OGE_HIP_TRY(ctx, hipMemsetAsync(ndup, 0, 8, ctx->stream));
     if (opts->compat_nonverbose_index) {
@@ -1690,7 +1690,7 @@ int oge_markdup_finish_pre(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off,
         hipLaunchKernelGGL(k_apply, dim3(std::min<uint32_t>(nb, 2048u)), dim3(kT), 0, ctx->stream, d_recs, d_off, n, meta, d_dup,
                            apply, opts->compat_nonverbose_index, (const unsigned int *)(cnt + 1), ndup);
     OGE_LAUNCH_CHECK(ctx);
-    ctx->end_stage(t);
+    stage.end();
     unsigned long long h = 0;
     OGE_HIP_TRY(ctx, hipMemcpyAsync(&h, ndup, 8, hipMemcpyDeviceToHost, ctx->stream));
     OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1734,7 +1734,7 @@ int oge_markdup_run(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off, uint64
         if (!keys || !vals || !bad) return OGE_ERR_HIP;
         OGE_HIP_TRY(ctx, hipMemsetAsync(bad, 0, 16, ctx->stream));
     }
-    OgeStageTimer *t = ctx->begin_stage("md_readends");
+    OgeStage stage(ctx, "md_readends");
     OgePassArgs a = {};
     a.recs = d_recs;
     a.off = d_off;
@@ -1773,7 +1773,7 @@ int oge_markdup_run(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off, uint64
         F.skeys = skeys;  // unsorted: the words stand, the deviation slots go unused (no windowed stage)
         if (!sorted) F.dev = nullptr;
     }
-    ctx->end_stage(t);
+    stage.end();
     return oge_markdup_finish_pre(ctx, d_recs, d_off, n, opts, meta, d_dup, apply, n_dup_out, nullptr, nullptr, skeys,
                                   try_win ? &F : nullptr);
 }

@@ -15,6 +15,19 @@ struct OgeStageTimer {
     hipEvent_t start, stop;
 };
 
+// The contig name table the last call of one side uploaded: the names back to back in workspace `ws_names`, their
+// n_ref + 1 offsets in `ws_name_off` and, where `ws_slots` is set, the name hash of sam_parse.h; `counter` counts
+// the uploads.  The next call with the same table uses it as it is.
+struct OgeContigTable {
+    const char *ws_names, *ws_name_off, *ws_slots, *counter;
+    bool valid = false;
+    std::string names;
+    std::vector<uint32_t> name_off;
+    const uint8_t *d_names = nullptr;
+    const uint32_t *d_name_off = nullptr, *d_slots = nullptr;
+    uint32_t n_slots = 0;
+};
+
 struct oge_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -24,10 +37,10 @@ struct oge_ctx {
     std::map<std::string, Buf> bufs;
     // stage -> list of (start, stop) event pairs recorded during the last pipeline call
     std::map<std::string, std::vector<OgeStageTimer>> stage_events;
-    std::deque<OgeStageTimer> event_pool;  // deque: begin_stage's pointers stay valid while stages nest
+    std::deque<OgeStageTimer> event_pool;  // deque: an open OgeStage's pointer stays valid while stages nest
     size_t event_pool_used = 0;
     bool timing = true;
-    int timing_hold = 0;  // > 0: a composite entry point (the pipeline) keeps its sub-calls' stage events
+    int timing_hold = 0;  // > 0: a composite entry point (OgeCall with hold) keeps its sub-calls' stage events
     int deflate_search = OGE_DEFL_FAST;  // the GPU deflate's match search (oge_ctx_set_deflate_search)
     bool pool = false;  // allocate from the device's stream-ordered pool and keep freed memory in it
     hipStream_t side[4] = {nullptr, nullptr, nullptr, nullptr};  // extra streams a stage pipelines over
@@ -64,18 +77,10 @@ struct oge_ctx {
     bool refs_valid = false;
     std::string ref_names;
     std::vector<int32_t> ref_lens;
-    // the contig name table the last oge_text_* call uploaded (workspaces "text_names" / "text_name_off"): the
-    // next call with the same table uses it as it is
-    bool text_names_valid = false;
-    std::string text_names;
-    std::vector<uint32_t> text_name_off;
-    const void *text_names_ptr = nullptr, *text_name_off_ptr = nullptr;
-    // the contig table the last oge_sam_* call uploaded (workspaces "sam_names" / "sam_name_off" / "sam_slots"),
-    // and what the last oge_sam_parse call returned (host memory, valid until the next one)
-    bool sam_names_valid = false;
-    std::string sam_names;
-    std::vector<uint32_t> sam_name_off;
-    const void *sam_names_ptr = nullptr, *sam_name_off_ptr = nullptr, *sam_slots_ptr = nullptr;
+    // the contig tables the last oge_text_* and the last oge_sam_* call uploaded (oge_contig_table), and what the
+    // last oge_sam_parse call returned (host memory, valid until the next one)
+    OgeContigTable text_table{"text_names", "text_name_off", nullptr, "text_table_uploads"};
+    OgeContigTable sam_table{"sam_names", "sam_name_off", "sam_slots", "sam_table_uploads"};
     std::vector<uint8_t> sam_out_recs, sam_out_warn;
     std::vector<uint64_t> sam_out_off;
     std::map<std::string, uint64_t> counters;  // per call: work counts a stage reports (oge_ctx_counter)
@@ -92,10 +97,47 @@ struct oge_ctx {
     void *scratch(const char *name, size_t bytes);
     void lend(void *p, size_t bytes) { loan_base = (uint8_t *)p; loan_cap = p ? bytes : 0; loan_used = 0; }
     void end_loan() { loan_base = nullptr; loan_cap = loan_used = 0; }
-    OgeStageTimer *begin_stage(const char *name);
-    void end_stage(OgeStageTimer *t);
+    bool in_composite() const { return timing_hold > 0; }  // under a composite entry point's OgeCall
     void reset_timing();
 };
+
+// One timed stage of a context's stream, open from begin() to end() or the end of the scope, whichever comes
+// first: an error return in between still records the stop event.  begin() closes the stage that is open, so a
+// function that runs its stages one after another keeps one object; a stage nested in another takes its own.
+// With ctx->timing off nothing is recorded.
+class OgeStage {
+public:
+    explicit OgeStage(oge_ctx *c) : ctx(c) {}
+    OgeStage(oge_ctx *c, const char *name) : ctx(c) { begin(name); }
+    OgeStage(const OgeStage &) = delete;
+    OgeStage &operator=(const OgeStage &) = delete;
+    ~OgeStage() { end(); }
+    void begin(const char *name);
+    void end();
+
+private:
+    oge_ctx *ctx;
+    OgeStageTimer *open = nullptr;
+};
+
+// An entry point's prologue, after its argument checks: makes the context's device current and drops the last
+// call's stage events and counters (not under a composite caller, which keeps them).  With `hold` the entry
+// point is itself composite: the entry points it calls add to its stages until it returns.
+class OgeCall {
+public:
+    OgeCall(oge_ctx *c, bool hold);
+    OgeCall(const OgeCall &) = delete;
+    OgeCall &operator=(const OgeCall &) = delete;
+    ~OgeCall() { ctx->timing_hold -= held; }
+
+private:
+    oge_ctx *ctx;
+    int held;
+};
+
+// Checks the contig fields of `o` (errors are prefixed with `who`) and, with a table, makes it the one on the
+// device: uploaded only when it differs from what the table's last call left there.
+int oge_contig_table(oge_ctx *ctx, OgeContigTable *tab, const oge_text_opts *o, const char *who);
 
 #define OGE_HIP_TRY(ctx, expr)                                                                     \
     do {                                                                                           \

@@ -37,15 +37,6 @@ using namespace oge;
 
 namespace {
 
-struct Hold {  // keep every sub-call's stage events for the caller
-    oge_ctx *c;
-    explicit Hold(oge_ctx *x) : c(x) {
-        c->reset_timing();
-        c->timing_hold++;
-    }
-    ~Hold() { c->timing_hold--; }
-};
-
 // MarkDuplicates::getLibraryName (algorithms/mark_duplicates.cpp:301-318): the LB of the record's
 // @RG, "Unknown Library" when absent or empty; distinct names get distinct ids.
 struct LibTable {
@@ -90,10 +81,10 @@ static int decode_records(oge_ctx *ctx, uint8_t *X, uint64_t total, uint64_t **x
 
 // The framing index of a BGZF file in HBM (device walk; host walk of a copy when the chain is not exact).
 static int index_file(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, OgeBgzfIndex *ixo) {
-    OgeStageTimer *tm = ctx->begin_stage("bgzf_index");
+    OgeStage stage(ctx, "bgzf_index");
     OgeBgzfIndex ix;
     int rc = oge_bgzf_index_ws(ctx, d_z, zbytes, &ix);
-    ctx->end_stage(tm);
+    stage.end();
     if (rc < 0) return rc;
     if (rc == 1) {
         uint64_t nb = 0;
@@ -138,7 +129,7 @@ static int decode(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint8_t **X
 // first bytes), record walk.
 static int decode_records(oge_ctx *ctx, uint8_t *X, uint64_t total, uint64_t **xoff_o, uint64_t *n_o, BamFile *f, uint64_t *rec_base_o) {
     int rc = OGE_OK;
-    OgeStageTimer *tm = nullptr;
+    OgeStage stage(ctx);
     // ---- header (host parse of the stream's first bytes)
     std::string err;
     size_t rec_base = 0;
@@ -153,7 +144,7 @@ static int decode_records(oge_ctx *ctx, uint8_t *X, uint64_t total, uint64_t **x
     const int32_t n_ref = (int32_t)f->ref_names.size();
 
     // ---- record boundaries
-    tm = ctx->begin_stage("rec_walk");
+    stage.begin("rec_walk");
     // the count walk keeps each chunk's record positions for the fill (in the sorted-records arena when it
     // is already there: sort_stage writes it only later)
     uint64_t n = 0, x = 0;
@@ -166,7 +157,7 @@ static int decode_records(oge_ctx *ctx, uint8_t *X, uint64_t total, uint64_t **x
     if (!xoff) return OGE_ERR_HIP;
     rc = oge_record_walk(ctx, X, rec_base, total, total, true, n_ref, xoff, n + 1, &n, &x, true);
     if (rc) return rc;
-    ctx->end_stage(tm);
+    stage.end();
     *xoff_o = xoff;
     *n_o = n;
     if (rec_base_o) *rec_base_o = rec_base;
@@ -226,9 +217,9 @@ static int sort_stage(oge_ctx *ctx, uint8_t *X, uint64_t *xoff, uint64_t n, uint
     if (rc) return rc;
     *src = Y, *spare = X, *soff = yoff, *m = n;
     if (mo->mark_duplicates && mo->remove_duplicates) {  // -R: MarkDuplicates::runInternal :456-458
-        OgeStageTimer *tm = ctx->begin_stage("drop_dups");
+        OgeStage stage(ctx, "drop_dups");
         rc = oge_drop_flagged_dev(ctx, Y, yoff, n, 0x400, X, xoff, m);
-        ctx->end_stage(tm);
+        stage.end();
         if (rc) return rc;
         *src = X, *spare = Y, *soff = xoff;
     }
@@ -257,8 +248,7 @@ extern "C" int oge_mergesort_bgzf_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!mo || !d_out || !out_bytes || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
     if (mo->level < 0 || mo->level > 9) return oge_fail(ctx, OGE_ERR_ARG, "level must be 0..9");
-    (void)hipSetDevice(ctx->device);
-    Hold hold(ctx);
+    OgeCall call(ctx, /*hold=*/true);
     *d_out = nullptr;
     *out_bytes = 0;
     ctx->bai_ptr = nullptr;  // oge_ctx_last_bai: this call's index or none
@@ -302,8 +292,7 @@ extern "C" int oge_mergesort_bgzf_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t
 extern "C" int oge_bam_index_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const uint8_t **d_bai, uint64_t *bai_bytes) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!d_bai || !bai_bytes || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
-    (void)hipSetDevice(ctx->device);
-    Hold hold(ctx);
+    OgeCall call(ctx, /*hold=*/true);
     *d_bai = nullptr;
     *bai_bytes = 0;
     ctx->bai_ptr = nullptr;
@@ -338,8 +327,7 @@ extern "C" int oge_bam_stats_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbyt
                                  const uint32_t **d_len, const uint64_t **d_len_count) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!stats || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
-    (void)hipSetDevice(ctx->device);
-    Hold hold(ctx);
+    OgeCall call(ctx, /*hold=*/true);
     uint8_t *X;
     uint64_t *xoff, n;
     BamFile f;
@@ -353,8 +341,7 @@ extern "C" int oge_bam_coverage_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t z
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!d_bins || !n_bins || !n_skipped || !overflow || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
     if (binsize < 1) return oge_fail(ctx, OGE_ERR_ARG, "coverage: binsize < 1");
-    (void)hipSetDevice(ctx->device);
-    Hold hold(ctx);
+    OgeCall call(ctx, /*hold=*/true);
     *d_bins = nullptr;
     *n_bins = 0;
     uint8_t *X;
@@ -378,8 +365,7 @@ extern "C" int oge_bam_coverage_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t z
 extern "C" int oge_bam_count_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint64_t *n_reads) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!n_reads || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
-    (void)hipSetDevice(ctx->device);
-    Hold hold(ctx);
+    OgeCall call(ctx, /*hold=*/true);
     uint8_t *X;
     uint64_t *xoff;
     BamFile f;
@@ -404,8 +390,7 @@ extern "C" int oge_mergesort_bgzf_host(oge_ctx *ctx, const uint8_t *h_z, uint64_
     if (!mo || !out_bytes || !h_out || (zbytes && !h_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
     if (mo->level < 0 || mo->level > 9) return oge_fail(ctx, OGE_ERR_ARG, "level must be 0..9");
     if (mo->build_index) return oge_fail(ctx, OGE_ERR_ARG, "index not provided on this path");
-    (void)hipSetDevice(ctx->device);
-    Hold hold(ctx);
+    OgeCall call(ctx, /*hold=*/true);
     *out_bytes = 0;
     // OGE_HOSTPIPE_TRACE: host timestamps of the steps on stderr (where the PCIe-inclusive time goes)
     const bool trace = getenv("OGE_HOSTPIPE_TRACE") != nullptr;
@@ -452,7 +437,7 @@ extern "C" int oge_mergesort_bgzf_host(oge_ctx *ctx, const uint8_t *h_z, uint64_
     }
     mark("upload queued");
     // ---- 2. the framing, on the host meanwhile
-    OgeStageTimer *tm = ctx->begin_stage("bgzf_index");
+    OgeStage stage(ctx, "bgzf_index");
     std::vector<uint64_t> d0, d1, uo;
     std::vector<uint32_t> crc;
     if (!oge_bgzf_index_host_mt(h_z, zbytes, (int)env_u64("OGE_HOSTPIPE_THREADS", 16), d0, d1, uo, crc)) {
@@ -474,7 +459,7 @@ extern "C" int oge_mergesort_bgzf_host(oge_ctx *ctx, const uint8_t *h_z, uint64_
         OGE_HIP_TRY(ctx, hipMemcpyAsync(dcrc, crc.data(), nb * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     OGE_HIP_TRY(ctx, hipMemcpyAsync(dix + 2 * nb, uo.data(), (nb + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    ctx->end_stage(tm);
+    stage.end();
     mark("host index done");
     // ---- 3. inflate: the blocks whose bytes are up, chunk after chunk (the X of the device chain)
     const uint64_t cap = std::max<uint64_t>(total, oge_bgzf_bound(total) + (1u << 20)) + 64;
@@ -609,9 +594,9 @@ static int dist_sort_write(oge_comm *comm, int rc, const std::string &why, uint8
         }
         Y = (uint8_t *)ctx->ws("pipe_y", bytes + 64);
         if (!Y) return OGE_ERR_HIP;
-        OgeStageTimer *tm = ctx->begin_stage("drop_dups");
+        OgeStage stage(ctx, "drop_dups");
         rc = oge_drop_flagged_dev(ctx, dout, doff, no, 0x400, Y, yoff, &m);
-        ctx->end_stage(tm);
+        stage.end();
         if (rc) return rc;
         src = Y, soff = yoff;
     }
@@ -647,7 +632,6 @@ static int dist_args(oge_comm *comm, const uint8_t *d_z, uint64_t zbytes, const 
     if (!mo || !d_out || !out_bytes || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
     if (mo->level < 0 || mo->level > 9) return oge_fail(ctx, OGE_ERR_ARG, "level must be 0..9");
     if (mo->build_index) return oge_fail(ctx, OGE_ERR_ARG, "index not provided on this path");
-    (void)hipSetDevice(ctx->device);
     *d_out = nullptr;
     *out_bytes = 0;
     return OGE_OK;
@@ -659,7 +643,7 @@ extern "C" int oge_mergesort_bgzf_dist(oge_comm *comm, const uint8_t *d_z, uint6
                                        const uint8_t **d_out, uint64_t *out_bytes, uint64_t *n_reads_total, uint64_t *n_dup_total) {
     if (const int rc = dist_args(comm, d_z, zbytes, mo, d_out, out_bytes)) return rc;
     oge_ctx *ctx = oge_comm_ctx(comm);
-    Hold hold(ctx);
+    OgeCall call(ctx, /*hold=*/true);
     oge_comm_reset_stats(comm);
     uint8_t *X = nullptr;
     uint64_t cap = 0, *xoff = nullptr, n = 0;
@@ -676,7 +660,7 @@ extern "C" int oge_mergesort_bgzf_shard(oge_comm *comm, const uint8_t *d_z, uint
                                         uint64_t *n_reads_total, uint64_t *n_dup_total) {
     if (const int rc = dist_args(comm, d_z, zbytes, mo, d_out, out_bytes)) return rc;
     oge_ctx *ctx = oge_comm_ctx(comm);
-    Hold hold(ctx);
+    OgeCall call(ctx, /*hold=*/true);
     oge_comm_reset_stats(comm);
     uint8_t *X = nullptr;
     uint64_t *xoff = nullptr, n = 0;

@@ -532,12 +532,6 @@ void drop_ws(oge_ctx *ctx, const char *name) {
     ctx->bufs.erase(it);
 }
 
-struct EndStage {
-    oge_ctx *c;
-    OgeStageTimer *t;
-    ~EndStage() { c->end_stage(t); }
-};
-
 inline dim3 grid_for(uint64_t items) { return dim3(std::max<uint32_t>(1, oge_ceil_div(items, kT))); }
 
 }  // namespace
@@ -553,8 +547,7 @@ int oge_qc_stats_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off
     if (lengths && (!d_len || !d_len_count)) return oge_fail(ctx, OGE_ERR_ARG, "stats: lengths requested without output pointers");
     if (n && (!d_recs || !d_off)) return oge_fail(ctx, OGE_ERR_ARG, "stats: null argument");
     if (n >= 0xFFFFFFFFull * kBlockRecs) return oge_fail(ctx, OGE_ERR_LIMIT, "stats: too many records");
-    OgeStageTimer *tm = ctx->begin_stage("qc_stats");
-    EndStage es{ctx, tm};
+    OgeStage stage(ctx, "qc_stats");
     hipStream_t st = ctx->stream;
     const uint32_t nblk = oge_ceil_div(n, kBlockRecs);
     const uint64_t nw = (uint64_t)nblk * kWaves;
@@ -669,8 +662,7 @@ int oge_qc_coverage_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_
     OGE_HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
     const std::string too_many = "coverage: " + std::to_string(nb) + " bins do not fit in free device memory: use a larger --binsize";
     if (nb > (1ull << 60) || nb * 4 > total_b) return oge_fail(ctx, OGE_ERR_LIMIT, too_many.c_str());
-    OgeStageTimer *tm = ctx->begin_stage("qc_coverage");
-    EndStage es{ctx, tm};
+    OgeStage stage(ctx, "qc_coverage");
     hipStream_t st = ctx->stream;
     // free memory is what the allocation finds (the context's pool may hold more than hipMemGetInfo reports)
     uint32_t *bins = (uint32_t *)ctx->ws("qc_bins", nb * 4);
@@ -720,8 +712,7 @@ int oge_stats_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, ui
                   const uint32_t **d_len, const uint64_t **d_len_count) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!stats) return oge_fail(ctx, OGE_ERR_ARG, "oge_stats_dev: null argument");
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     return oge_qc_stats_impl(ctx, d_recs, d_off, n, want, stats, d_len, d_len_count);
 }
 
@@ -755,8 +746,7 @@ int oge_coverage_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off,
                      int32_t binsize, const uint32_t **d_bins, uint64_t *n_skipped, int32_t *overflow) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!d_bins || !n_skipped || !overflow) return oge_fail(ctx, OGE_ERR_ARG, "oge_coverage_dev: null argument");
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     return oge_qc_coverage_impl(ctx, d_recs, d_off, n, n_ref, ref_len, binsize, d_bins, n_skipped, overflow);
 }
 

@@ -348,7 +348,7 @@ static int scan_core(oge_ctx *ctx, const RsDevBatch &b, const uint64_t *h_cons_o
     if (!dcp || !drp || !drf || !dgen) return OGE_ERR_HIP;
     OGE_HIP_TRY(ctx, hipMemsetAsync(dgen, 0, 4, s));
     uint32_t generic = 0;
-    OgeStageTimer *t = ctx->begin_stage("realign_scan");
+    OgeStage stage(ctx, "realign_scan");
     const uint64_t items = (uint64_t)b.n_cons + b.n_reads;
     hipLaunchKernelGGL(k_planes, dim3((uint32_t)((items + 3) / 4)), dim3(kT), 0, s, b.cons, b.cons_off, b.n_cons, b.cwo, b.bases, b.quals,
                        b.read_off, b.n_reads, b.rwo, dcp, drp, drf, dgen);
@@ -400,7 +400,7 @@ static int scan_core(oge_ctx *ctx, const RsDevBatch &b, const uint64_t *h_cons_o
         }
         OGE_HIP_TRY(ctx, hipStreamSynchronize(s));  // `all` must outlive the upload
     }
-    ctx->end_stage(t);
+    stage.end();
     ctx->last_scan_generic = generic != 0;
     if (generic_out) *generic_out = generic != 0;
     return OGE_OK;
@@ -488,8 +488,7 @@ extern "C" {
 
 int oge_realign_scan(oge_ctx *ctx, const oge_realign_scan_batch *b, int32_t *best_index, int32_t *best_score) {
     if (!ctx || !b) return oge_fail(ctx, OGE_ERR_ARG, "oge_realign_scan: null argument");
-    hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     return realign_scan_host(ctx, b->cons, b->cons_bytes, b->cons_off, b->n_cons, b->bases, b->quals, b->read_bytes,
                              b->read_off, b->n_reads, b->pairs, b->n_pairs, best_index, best_score);
 }

@@ -757,7 +757,7 @@ int oge_realign_prep_run(oge_ctx *ctx, const uint8_t *d_recs, const oge::DevPrep
         OGE_HIP_TRY(ctx, hipMemcpyAsync(drec, B.rec.data(), nr * 8, hipMemcpyHostToDevice, s));
         OGE_HIP_TRY(ctx, hipMemcpyAsync(dstart, B.start.data(), nr * 4, hipMemcpyHostToDevice, s));
     }
-    OgeStageTimer *tm = ctx->begin_stage("realign_prep");
+    OgeStage stage(ctx, "realign_prep");
     ReadArgs RA{d_recs, drec, dstart, drd_off, nw, nr, dref, dref_off, dout, dclen};
     if (nr) {
         hipLaunchKernelGGL(k_r2_read, dim3((uint32_t)((nr + kT - 1) / kT)), dim3(kT), 0, s, RA);
@@ -812,7 +812,7 @@ int oge_realign_prep_run(oge_ctx *ctx, const uint8_t *d_recs, const oge::DevPrep
     OGE_HIP_TRY(ctx, hipMemcpyAsync(dcwo + n_cons, &ends[1], 8, hipMemcpyHostToDevice, s));
     OGE_HIP_TRY(ctx, hipMemcpyAsync(dro + n_reads, &ends[2], 8, hipMemcpyHostToDevice, s));
     OGE_HIP_TRY(ctx, hipMemcpyAsync(drwo + n_reads, &ends[3], 8, hipMemcpyHostToDevice, s));
-    ctx->end_stage(tm);
+    stage.end();
     const double t1 = clk();
     // the offset scan over the batch in place
     O.best_index.resize(n_pairs);  // (written by the scan)

@@ -76,61 +76,25 @@ __global__ __launch_bounds__(kT) void k_text_emit(const uint8_t *__restrict__ re
     }
 }
 
-struct EndStage {
-    oge_ctx *c;
-    OgeStageTimer *t;
-    ~EndStage() { c->end_stage(t); }
-};
-
-struct Hold {  // a composite entry point keeps its sub-calls' stage events and counters
-    oge_ctx *c;
-    explicit Hold(oge_ctx *x) : c(x) { ++c->timing_hold; }
-    ~Hold() { --c->timing_hold; }
-};
-
+// this side's own option checks, then the contig fields
 int check_opts(oge_ctx *ctx, const oge_text_opts *o, const char *who) {
     const std::string w(who);
     if (!o) return oge_fail(ctx, OGE_ERR_ARG, (w + ": null argument").c_str());
     if (o->mode != OGE_TEXT_SAM && o->mode != OGE_TEXT_FASTQ) return oge_fail(ctx, OGE_ERR_ARG, (w + ": unknown text mode").c_str());
     if (o->trim_begin < 0 || o->trim_end < 0) return oge_fail(ctx, OGE_ERR_ARG, (w + ": negative trim length").c_str());
-    if (o->n_ref < 0 || (o->n_ref && (!o->ref_names || !o->ref_name_off)))
-        return oge_fail(ctx, OGE_ERR_ARG, (w + ": n_ref < 0 or no contig names").c_str());
-    for (int32_t r = 0; r < o->n_ref; ++r)
-        if (o->ref_name_off[r + 1] < o->ref_name_off[r]) return oge_fail(ctx, OGE_ERR_ARG, (w + ": contig name offsets decrease").c_str());
-    return OGE_OK;
+    return oge_contig_table(ctx, nullptr, o, who);
 }
 
-// the contig table on the device, uploaded when it differs from the one that is there
-int device_params(oge_ctx *ctx, const oge_text_opts *o, OgeTextParams *tp) {
-    const uint32_t bytes = o->n_ref ? o->ref_name_off[o->n_ref] : 0;
-    std::vector<uint32_t> offs(o->ref_name_off ? o->ref_name_off : nullptr, o->ref_name_off ? o->ref_name_off + o->n_ref + 1 : nullptr);
-    if (offs.empty()) offs.push_back(0);
-    uint8_t *d_names = (uint8_t *)ctx->ws("text_names", (size_t)bytes + 8);
-    uint32_t *d_name_off = (uint32_t *)ctx->ws("text_name_off", offs.size() * 4);
-    if (!d_names || !d_name_off) return OGE_ERR_HIP;
-    const bool same = ctx->text_names_valid && ctx->text_names_ptr == d_names && ctx->text_name_off_ptr == d_name_off &&
-                      ctx->text_name_off == offs && ctx->text_names.size() == bytes &&
-                      (!bytes || !memcmp(ctx->text_names.data(), o->ref_names, bytes));
-    if (!same) {
-        ctx->text_names_valid = false;
-        ctx->text_names.assign(bytes ? o->ref_names : "", bytes);
-        ctx->text_name_off = offs;
-        std::string padded = ctx->text_names;
-        padded.append(8, '\0');
-        OGE_HIP_TRY(ctx, hipMemcpyAsync(d_names, padded.data(), padded.size(), hipMemcpyHostToDevice, ctx->stream));
-        OGE_HIP_TRY(ctx, hipMemcpyAsync(d_name_off, offs.data(), offs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the staging string goes out of scope
-        ctx->text_names_ptr = d_names;
-        ctx->text_name_off_ptr = d_name_off;
-        ctx->text_names_valid = true;
-        ctx->counters["text_table_uploads"] += 1;
-    }
+// the kernels' parameters, with the contig table on the device
+int device_params(oge_ctx *ctx, const oge_text_opts *o, const char *who, OgeTextParams *tp) {
+    const int rc = oge_contig_table(ctx, &ctx->text_table, o, who);
+    if (rc) return rc;
     tp->mode = o->mode;
     tp->trim_begin = o->trim_begin;
     tp->trim_end = o->trim_end;
     tp->n_ref = o->n_ref;
-    tp->names = d_names;
-    tp->name_off = d_name_off;
+    tp->names = ctx->text_table.d_names;
+    tp->name_off = ctx->text_table.d_name_off;
     return OGE_OK;
 }
 
@@ -143,10 +107,9 @@ int text_size_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, u
     if (!d_text_off || (n && (!d_recs || !d_off || !d_host_mark))) return oge_fail(ctx, OGE_ERR_ARG, "oge_text_size_dev: null argument");
     if (n >= 0xFFFFFFFFull) return oge_fail(ctx, OGE_ERR_LIMIT, "oge_text_size_dev: more than 2^32-2 records");
     OgeTextParams tp;
-    rc = device_params(ctx, opts, &tp);
+    rc = device_params(ctx, opts, "oge_text_size_dev", &tp);
     if (rc) return rc;
-    OgeStageTimer *tm = ctx->begin_stage("text_size");
-    EndStage es{ctx, tm};
+    OgeStage stage(ctx, "text_size");
     hipStream_t st = ctx->stream;
     TextAcc *acc = (TextAcc *)ctx->ws("text_acc", sizeof(TextAcc));
     if (!acc) return OGE_ERR_HIP;
@@ -190,10 +153,9 @@ int text_emit_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, c
     if (ends[1] == ends[0]) return OGE_OK;
     if (!d_out) return oge_fail(ctx, OGE_ERR_ARG, "oge_text_emit_dev: null argument");
     OgeTextParams tp;
-    rc = device_params(ctx, opts, &tp);
+    rc = device_params(ctx, opts, "oge_text_emit_dev", &tp);
     if (rc) return rc;
-    OgeStageTimer *tm = ctx->begin_stage("text_emit");
-    EndStage es{ctx, tm};
+    OgeStage stage(ctx, "text_emit");
     hipLaunchKernelGGL(k_text_emit, dim3(oge_ceil_div(count, kBlockRecs)), dim3(kT), 0, st, d_recs, d_off, d_text_off, first, count, tp, d_out);
     OGE_LAUNCH_CHECK(ctx);
     return OGE_OK;
@@ -207,16 +169,14 @@ int oge_text_size_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off
                       uint64_t *d_text_off, uint8_t *d_host_mark, uint64_t *total, uint64_t *n_host) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!total || !n_host) return oge_fail(ctx, OGE_ERR_ARG, "oge_text_size_dev: null argument");
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     return text_size_impl(ctx, d_recs, d_off, n, opts, d_text_off, d_host_mark, total, n_host);
 }
 
 int oge_text_emit_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, const uint64_t *d_text_off, uint64_t first,
                       uint64_t count, const oge_text_opts *opts, uint8_t *d_out, uint64_t cap) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     return text_emit_impl(ctx, d_recs, d_off, d_text_off, first, count, opts, d_out, cap);
 }
 
@@ -237,9 +197,7 @@ int oge_text_format(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!bytes || (n && (!recs || !rec_off))) return oge_fail(ctx, OGE_ERR_ARG, "oge_text_format: null argument");
     *bytes = 0;
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
-    Hold hold(ctx);
+    OgeCall call(ctx, /*hold=*/true);
     hipStream_t st = ctx->stream;
     uint8_t *dr = (uint8_t *)ctx->ws("host_recs", rec_bytes + 16);
     uint64_t *dof = (uint64_t *)ctx->ws("host_off", (n + 1) * 8);

@@ -105,64 +105,16 @@ __global__ __launch_bounds__(kT) void k_sam_emit(const uint8_t *__restrict__ tex
     }
 }
 
-struct EndStage {
-    oge_ctx *c;
-    OgeStageTimer *t;
-    ~EndStage() { c->end_stage(t); }
-};
-
-struct Hold {  // a composite entry point keeps its sub-calls' stage events and counters
-    oge_ctx *c;
-    explicit Hold(oge_ctx *x) : c(x) { ++c->timing_hold; }
-    ~Hold() { --c->timing_hold; }
-};
-
-int check_opts(oge_ctx *ctx, const oge_text_opts *o, const char *who) {
-    const std::string w(who);
-    if (!o) return oge_fail(ctx, OGE_ERR_ARG, (w + ": null argument").c_str());
-    if (o->n_ref < 0 || (o->n_ref && (!o->ref_names || !o->ref_name_off)))
-        return oge_fail(ctx, OGE_ERR_ARG, (w + ": n_ref < 0 or no contig names").c_str());
-    for (int32_t r = 0; r < o->n_ref; ++r)
-        if (o->ref_name_off[r + 1] < o->ref_name_off[r]) return oge_fail(ctx, OGE_ERR_ARG, (w + ": contig name offsets decrease").c_str());
-    return OGE_OK;
-}
-
-// the contig table and its hash on the device, uploaded when the names differ from the ones that are there
-int device_table(oge_ctx *ctx, const oge_text_opts *o, OgeSamParams *sp) {
-    const uint32_t bytes = o->n_ref ? o->ref_name_off[o->n_ref] : 0;
-    std::vector<uint32_t> offs(o->ref_name_off ? o->ref_name_off : nullptr, o->ref_name_off ? o->ref_name_off + o->n_ref + 1 : nullptr);
-    if (offs.empty()) offs.push_back(0);
-    const uint32_t slots = oge_sam_table_slots(o->n_ref);
-    uint8_t *d_names = (uint8_t *)ctx->ws("sam_names", (size_t)bytes + 8);
-    uint32_t *d_name_off = (uint32_t *)ctx->ws("sam_name_off", offs.size() * 4);
-    uint32_t *d_slots = (uint32_t *)ctx->ws("sam_slots", (size_t)slots * 4);
-    if (!d_names || !d_name_off || !d_slots) return OGE_ERR_HIP;
-    const bool same = ctx->sam_names_valid && ctx->sam_names_ptr == d_names && ctx->sam_name_off_ptr == d_name_off &&
-                      ctx->sam_slots_ptr == d_slots && ctx->sam_name_off == offs && ctx->sam_names.size() == bytes &&
-                      (!bytes || !memcmp(ctx->sam_names.data(), o->ref_names, bytes));
-    if (!same) {
-        ctx->sam_names_valid = false;
-        ctx->sam_names.assign(bytes ? o->ref_names : "", bytes);
-        ctx->sam_name_off = offs;
-        std::vector<uint32_t> table(slots, 0);
-        oge_sam_table_build(o->n_ref, (const uint8_t *)ctx->sam_names.data(), offs.data(), table.data());
-        std::string padded = ctx->sam_names;
-        padded.append(8, '\0');
-        OGE_HIP_TRY(ctx, hipMemcpyAsync(d_names, padded.data(), padded.size(), hipMemcpyHostToDevice, ctx->stream));
-        OGE_HIP_TRY(ctx, hipMemcpyAsync(d_name_off, offs.data(), offs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        OGE_HIP_TRY(ctx, hipMemcpyAsync(d_slots, table.data(), table.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffers go out of scope
-        ctx->sam_names_ptr = d_names;
-        ctx->sam_name_off_ptr = d_name_off;
-        ctx->sam_slots_ptr = d_slots;
-        ctx->sam_names_valid = true;
-        ctx->counters["sam_table_uploads"] += 1;
-    }
+// the kernels' parameters, with the contig table and its hash on the device
+int device_table(oge_ctx *ctx, const oge_text_opts *o, const char *who, OgeSamParams *sp) {
+    const OgeContigTable &t = ctx->sam_table;
+    const int rc = oge_contig_table(ctx, &ctx->sam_table, o, who);
+    if (rc) return rc;
     sp->n_ref = o->n_ref;
-    sp->hmask = slots - 1;
-    sp->names = d_names;
-    sp->name_off = d_name_off;
-    sp->slots = d_slots;
+    sp->hmask = t.n_slots - 1;
+    sp->names = t.d_names;
+    sp->name_off = t.d_name_off;
+    sp->slots = t.d_slots;
     return OGE_OK;
 }
 
@@ -171,8 +123,7 @@ int lines_impl(oge_ctx *ctx, const uint8_t *d_text, uint64_t bytes, uint64_t bod
     if (body_off > bytes) return oge_fail(ctx, OGE_ERR_ARG, "oge_sam_lines_dev: body_off is past the text");
     if (bytes > body_off && !d_text) return oge_fail(ctx, OGE_ERR_ARG, "oge_sam_lines_dev: null argument");
     if ((uintptr_t)d_text & 3) return oge_fail(ctx, OGE_ERR_ARG, "oge_sam_lines_dev: the text is not 4-byte aligned");
-    OgeStageTimer *tm = ctx->begin_stage("sam_lines");
-    EndStage es{ctx, tm};
+    OgeStage stage(ctx, "sam_lines");
     hipStream_t st = ctx->stream;
     const uint64_t tile0 = body_off / OGE_SAM_TILE;
     const uint64_t n_tiles = bytes > body_off ? (bytes + OGE_SAM_TILE - 1) / OGE_SAM_TILE - tile0 : 0;
@@ -208,17 +159,16 @@ int size_impl(oge_ctx *ctx, const uint8_t *d_text, const uint64_t *d_line_off, u
               uint8_t *d_host_mark, uint8_t *d_warn, uint64_t *total, uint64_t *n_host) {
     *total = 0;
     *n_host = 0;
-    int rc = check_opts(ctx, opts, "oge_sam_size_dev");
+    int rc = oge_contig_table(ctx, nullptr, opts, "oge_sam_size_dev");
     if (rc) return rc;
     ctx->counters["sam_wave_lines"] = kWaveLines;
     ctx->counters["sam_block_lines"] = kBlockLines;
     if (!d_rec_off || (n && (!d_text || !d_line_off || !d_host_mark || !d_warn))) return oge_fail(ctx, OGE_ERR_ARG, "oge_sam_size_dev: null argument");
     if (n >= 0xFFFFFFFFull) return oge_fail(ctx, OGE_ERR_LIMIT, "oge_sam_size_dev: more than 2^32-2 lines");
     OgeSamParams sp;
-    rc = device_table(ctx, opts, &sp);
+    rc = device_table(ctx, opts, "oge_sam_size_dev", &sp);
     if (rc) return rc;
-    OgeStageTimer *tm = ctx->begin_stage("sam_size");
-    EndStage es{ctx, tm};
+    OgeStage stage(ctx, "sam_size");
     hipStream_t st = ctx->stream;
     SamAcc *acc = (SamAcc *)ctx->ws("sam_acc", sizeof(SamAcc));
     uint8_t *d_err = (uint8_t *)ctx->ws("sam_err", n + 1);
@@ -274,7 +224,7 @@ int size_impl(oge_ctx *ctx, const uint8_t *d_text, const uint64_t *d_line_off, u
 
 int emit_impl(oge_ctx *ctx, const uint8_t *d_text, const uint64_t *d_line_off, const uint64_t *d_rec_off, uint64_t first, uint64_t count,
               const oge_text_opts *opts, uint8_t *d_recs, uint64_t cap) {
-    int rc = check_opts(ctx, opts, "oge_sam_emit_dev");
+    int rc = oge_contig_table(ctx, nullptr, opts, "oge_sam_emit_dev");
     if (rc) return rc;
     ctx->counters["sam_wave_lines"] = kWaveLines;
     ctx->counters["sam_block_lines"] = kBlockLines;
@@ -291,10 +241,9 @@ int emit_impl(oge_ctx *ctx, const uint8_t *d_text, const uint64_t *d_line_off, c
     if (ends[1] == ends[0]) return OGE_OK;
     if (!d_recs) return oge_fail(ctx, OGE_ERR_ARG, "oge_sam_emit_dev: null argument");
     OgeSamParams sp;
-    rc = device_table(ctx, opts, &sp);
+    rc = device_table(ctx, opts, "oge_sam_emit_dev", &sp);
     if (rc) return rc;
-    OgeStageTimer *tm = ctx->begin_stage("sam_emit");
-    EndStage es{ctx, tm};
+    OgeStage stage(ctx, "sam_emit");
     hipLaunchKernelGGL(k_sam_emit, dim3(oge_ceil_div(count, kBlockLines)), dim3(kT), 0, st, d_text, d_line_off, d_rec_off, first, count, sp, d_recs);
     OGE_LAUNCH_CHECK(ctx);
     return OGE_OK;
@@ -307,8 +256,7 @@ extern "C" {
 int oge_sam_lines_dev(oge_ctx *ctx, const uint8_t *d_text, uint64_t bytes, uint64_t body_off, uint64_t *d_line_off, uint64_t cap, uint64_t *n) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!n) return oge_fail(ctx, OGE_ERR_ARG, "oge_sam_lines_dev: null argument");
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     return lines_impl(ctx, d_text, bytes, body_off, d_line_off, cap, n);
 }
 
@@ -316,22 +264,20 @@ int oge_sam_size_dev(oge_ctx *ctx, const uint8_t *d_text, const uint64_t *d_line
                      uint8_t *d_host_mark, uint8_t *d_warn, uint64_t *total, uint64_t *n_host) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!total || !n_host) return oge_fail(ctx, OGE_ERR_ARG, "oge_sam_size_dev: null argument");
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     return size_impl(ctx, d_text, d_line_off, n, opts, d_rec_off, d_host_mark, d_warn, total, n_host);
 }
 
 int oge_sam_emit_dev(oge_ctx *ctx, const uint8_t *d_text, const uint64_t *d_line_off, const uint64_t *d_rec_off, uint64_t first, uint64_t count,
                      const oge_text_opts *opts, uint8_t *d_recs, uint64_t cap) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     return emit_impl(ctx, d_text, d_line_off, d_rec_off, first, count, opts, d_recs, cap);
 }
 
 int oge_sam_host_record(const char *line, uint64_t len, const oge_text_opts *opts, uint8_t *buf, uint64_t cap, uint64_t *len_out) {
     if (!line || !len_out) return oge_fail(nullptr, OGE_ERR_ARG, "oge_sam_host_record: null argument");
-    const int rc = check_opts(nullptr, opts, "oge_sam_host_record");
+    const int rc = oge_contig_table(nullptr, nullptr, opts, "oge_sam_host_record");
     if (rc) return rc;
     std::vector<uint8_t> rec;
     std::string err;
@@ -364,9 +310,7 @@ int oge_sam_parse(oge_ctx *ctx, const char *text, uint64_t bytes, uint64_t *head
     *recs = nullptr;
     *rec_off = nullptr;
     if (warn) *warn = nullptr;
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
-    Hold hold(ctx);
+    OgeCall call(ctx, /*hold=*/true);
     hipStream_t st = ctx->stream;
     uint64_t body = 0, header_lines = 0;
     oge_sam_header(text, bytes, &body, &header_lines);

@@ -173,7 +173,7 @@ int oge_decode_shard(oge_comm *comm, const uint8_t *d_z, uint64_t zbytes, uint64
     if ((rc = S.agree(rc))) return rc;
 
     // ---- framing: the exact block chain of every range, joined across ranks
-    OgeStageTimer *tm = ctx->begin_stage("bgzf_index");
+    OgeStage stage(ctx, "bgzf_index");
     OgeBgzfIndex ix;
     std::vector<uint64_t> h0, h1, hu;
     std::vector<uint32_t> hc;
@@ -232,7 +232,7 @@ int oge_decode_shard(oge_comm *comm, const uint8_t *d_z, uint64_t zbytes, uint64
     uint64_t s_blk = 0;
     uint64_t x_blk = 0;
     rc = join_ranks(S, "shard_framing", "BGZF framing", 0, s0, x0, st, zf, frame, &s_blk, &x_blk);
-    ctx->end_stage(tm);
+    stage.end();
     if (rc) return rc;
     ctx->counters["shard_blocks"] = ix.nblk;
     ctx->counters["shard_zbytes"] = x_blk - s_blk;
@@ -245,7 +245,7 @@ int oge_decode_shard(oge_comm *comm, const uint8_t *d_z, uint64_t zbytes, uint64
     if ((rc = S.agree(rc))) return rc;
 
     // ---- edges: bases of the parts, the tails that straddle them, the header
-    tm = ctx->begin_stage("shard_edges");
+    stage.begin("shard_edges");
     std::vector<uint64_t> Ts;
     if ((rc = S.gather("shard_plan", T, Ts))) return rc;
     std::vector<uint64_t> Bs(S.G + 1, 0);
@@ -335,11 +335,11 @@ int oge_decode_shard(oge_comm *comm, const uint8_t *d_z, uint64_t zbytes, uint64
         f = BamFile();
         if (!bam_parse_header(hdr.data(), hdr.size(), f, err, &rec_base)) return oge_fail(ctx, OGE_ERR_IO, ("BAM header: " + err).c_str());
     }
-    ctx->end_stage(tm);
+    stage.end();
     const int32_t n_ref = (int32_t)f.ref_names.size();
 
     // ---- records that start in this part, joined across ranks
-    tm = ctx->begin_stage("rec_walk");
+    stage.begin("rec_walk");
     const bool at_end = look_hi == Ut;
     auto walk = [&](uint64_t sg, bool, uint64_t *xg) -> int {
         if (sg < B) return 1;
@@ -390,7 +390,7 @@ int oge_decode_shard(oge_comm *comm, const uint8_t *d_z, uint64_t zbytes, uint64
             rc = xoff ? oge_record_walk(ctx, X, s_rec - B, T, T + L, at_end, n_ref, xoff, n + 1, &n, &xe, true) : OGE_ERR_HIP;
         }
     }
-    ctx->end_stage(tm);
+    stage.end();
     if ((rc = S.agree(rc))) return rc;
     ctx->counters["shard_bytes"] = T;
     ctx->counters["shard_records"] = n;
@@ -406,15 +406,12 @@ extern "C" int oge_bgzf_decode_shard(oge_comm *comm, const uint8_t *d_z, uint64_
     if (!comm) return oge_fail(nullptr, OGE_ERR_ARG, "null communicator");
     oge_ctx *ctx = oge_comm_ctx(comm);
     if (!d_recs || !d_off || !n) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
-    (void)hipSetDevice(ctx->device);
-    ctx->reset_timing();
-    ctx->timing_hold++;
+    OgeCall call(ctx, /*hold=*/true);
     oge_comm_reset_stats(comm);
     uint8_t *X = nullptr;
     uint64_t *xoff = nullptr, m = 0;
     std::vector<uint8_t> h;
     const int rc = oge_decode_shard(comm, d_z, zbytes, own_bytes, &X, &xoff, &m, &h);
-    ctx->timing_hold--;
     if (rc) return rc;
     if (hdr_len) *hdr_len = h.size();
     if (hdr_out && hdr_cap < h.size()) return oge_fail(ctx, OGE_ERR_LIMIT, "hdr_cap is smaller than the BAM header");

@@ -427,14 +427,14 @@ int oge_sort_keys_dev_hook(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *
     unsigned int *counts = oge_sort_counts(ctx);
     if (!ktmp || !vtmp || !counts) return OGE_ERR_HIP;
     if (!keys_ready) {
-        OgeStageTimer *t = ctx->begin_stage("sort_keypack");
+        OgeStage stage(ctx, "sort_keypack");
         OGE_HIP_TRY(ctx, hipMemsetAsync(counts, 0, 32, ctx->stream));
         if (n) {
             hipLaunchKernelGGL(k_keypack, dim3(oge_ceil_div(n, kT)), dim3(kT), 0, ctx->stream, d_recs, d_off, n, n_ref, keys,
                                vals, counts + 2);
             OGE_LAUNCH_CHECK(ctx);
         }
-        ctx->end_stage(t);
+        stage.end();
     }
     // the varying key bits: from the input pass when it reduced them (keys_ready, counts[3] set), else a
     // reduction pass over the keys
@@ -453,10 +453,10 @@ int oge_sort_keys_dev_hook(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *
     }
     if (bad & 1) return oge_fail(ctx, OGE_ERR_ARG, "sort: record with refID outside [-1, n_ref) or pos < -1");
     if (bad & 2) return oge_fail(ctx, OGE_ERR_ARG, "sort: record block_size outside [32, 10000] (util/bam_deserializer.h:160)");
-    OgeStageTimer *t = ctx->begin_stage("sort_radix");
+    OgeStage stage(ctx, "sort_radix");
     rc = oge_radix_sort_pairs(ctx, keys, vals, ktmp, vtmp, n, (o ^ a) & kSortKeyMask, kout, vout);
     if (rc) return rc;
-    ctx->end_stage(t);
+    stage.end();
 
     // equal-coordinate runs -> (name, flag, index) order.  With summaries: gather them first and
     // order the small runs on them (k_ties_meta); long runs on the record bytes (k_tie_large), whose
@@ -465,12 +465,12 @@ int oge_sort_keys_dev_hook(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *
     if (!large) return OGE_ERR_HIP;
     OGE_HIP_TRY(ctx, hipMemsetAsync(counts, 0, 8, ctx->stream));
     if (meta_out && !hook) {
-        t = ctx->begin_stage("meta_gather");
+        stage.begin("meta_gather");
         rc = oge_meta_gather(ctx, meta_in, *vout, n, meta_out);
         if (rc) return rc;
-        ctx->end_stage(t);
+        stage.end();
     }
-    t = ctx->begin_stage("sort_ties");
+    stage.begin("sort_ties");
     if (n > 1) {
         if (hook)
             hipLaunchKernelGGL(k_ties_meta<false>, dim3(oge_ceil_div(n, kTieTile)), dim3(kT), 0, ctx->stream, d_recs, *kout,
@@ -517,11 +517,11 @@ int oge_sort_keys_dev_hook(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *
         }
         OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-    ctx->end_stage(t);
+    stage.end();
     if (hook) {
-        t = ctx->begin_stage("meta_gather");
+        stage.begin("meta_gather");
         if ((rc = hook->fn(hook->user, ctx, *vout, *kout))) return rc;
-        ctx->end_stage(t);
+        stage.end();
     }
     return OGE_OK;
 }
@@ -534,7 +534,7 @@ unsigned int *oge_sort_counts(oge_ctx *ctx) { return (unsigned int *)ctx->ws("so
 int oge_gather_with_sizes(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, const uint32_t *d_perm,
                           const uint64_t *sorted_keys, uint64_t n, uint8_t *d_out, uint64_t *d_out_off,
                           const RecMeta *smeta, const uint8_t *d_dup, const uint64_t *desc, unsigned int *ndup) {
-    OgeStageTimer *t = ctx->begin_stage("gather_offsets");
+    OgeStage stage(ctx, "gather_offsets");
     // the sizes straight from the sorted keys' payload inside the scan (r05: a sizes kernel first, 0.8 ms)
     int rc = sorted_keys ? oge_offsets_from_keys(ctx, sorted_keys, n, d_out_off) : 1;
     if (rc < 0) return rc;
@@ -549,9 +549,9 @@ int oge_gather_with_sizes(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d
         rc = oge_exclusive_scan_u64(ctx, d_out_off, d_out_off, n + 1);
         if (rc) return rc;
     }
-    ctx->end_stage(t);
+    stage.end();
     if (!n) return OGE_OK;
-    t = ctx->begin_stage("gather_records");
+    stage.begin("gather_records");
     OgePassArgs a = {};
     a.recs = d_recs;
     a.off = d_off;
@@ -565,6 +565,6 @@ int oge_gather_with_sizes(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d
     a.ndup = desc ? ndup : nullptr;
     rc = oge_gather_pass(ctx, a);
     if (rc) return rc;
-    ctx->end_stage(t);
+    stage.end();
     return OGE_OK;
 }

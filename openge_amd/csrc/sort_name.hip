@@ -56,15 +56,14 @@ extern "C" int oge_sort_name_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (n && (!d_recs || !d_off || !d_perm)) return oge_fail(ctx, OGE_ERR_ARG, "null buffer");
     if (n >= 0xffffffffull) return oge_fail(ctx, OGE_ERR_ARG, "too many records");
-    hipSetDevice(ctx->device);
-    ctx->reset_timing();
+    OgeCall call(ctx, /*hold=*/false);
     if (!n) return OGE_OK;
     uint32_t *dmax = (uint32_t *)ctx->ws("name_maxlen", 16);
     uint64_t *keys = (uint64_t *)ctx->ws("name_keys", n * 8);
     uint64_t *ktmp = (uint64_t *)ctx->ws("name_ktmp", n * 8);
     uint32_t *vtmp = (uint32_t *)ctx->ws("name_vtmp", n * 4);
     if (!dmax || !keys || !ktmp || !vtmp) return OGE_ERR_HIP;
-    OgeStageTimer *t = ctx->begin_stage("name_sort");
+    OgeStage stage(ctx, "name_sort");
     OGE_HIP_TRY(ctx, hipMemsetAsync(dmax, 0, 4, ctx->stream));
     k_name_maxlen<<<oge_ceil_div(n, 256), 256, 0, ctx->stream>>>(d_recs, d_off, n, dmax);
     OGE_LAUNCH_CHECK(ctx);
@@ -94,6 +93,6 @@ extern "C" int oge_sort_name_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint
         identity = false;
     }
     if (vals != d_perm) OGE_HIP_TRY(ctx, hipMemcpyAsync(d_perm, vals, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    ctx->end_stage(t);
+    stage.end();
     return OGE_OK;
 }
