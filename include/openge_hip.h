@@ -554,6 +554,48 @@ int oge_bam_count_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint64_
  * there is none. */
 int oge_ctx_last_refs(oge_ctx *ctx, int32_t *n_ref, const char **names, uint64_t *names_bytes, const int32_t **ref_len);
 
+/* ---- read-placement diff of two record sets in HBM (openge compare) ---------------------------------
+ * The reference's CompareCommand (commands/command_compare.cpp) as a multiset difference on the device;
+ * DESIGN.md section 23.  Set a is the reference set ("file 0"), set b the one compared with it.
+ * Element of a record: (refID, pos, CIGAR ops), pos the raw 0-based BAM position, each op (length, type char).
+ * Two elements are equal when all of it is equal.  Their order (the reference's operator<, the order of the
+ * printed diff): refID, pos, the number of ops, then op by op the length (unsigned) and the type CHARACTER,
+ * '=' < 'D' < 'H' < 'I' < 'M' < 'N' < 'P' < 'S' < 'X'.
+ * Region: a record belongs when left_ref <= refID <= right_ref and left_pos <= pos <= right_pos: the start
+ * position alone, both ends inclusive (not the overlap test of oge_filter_records_dev).  "No region" is
+ * (0, 0, INT32_MAX, INT32_MAX): refID -1 and pos -1 never belong to it.
+ * Counts (64-bit; the reference's are int): n_ref / n_other = the records of a / b inside the region, common =
+ * the multiset intersection (the sum over distinct elements of the smaller multiplicity), additions =
+ * n_other - common, deletions = n_ref - common.  hard_runs = runs of equal (refID, pos, op count, hash) that
+ * held two different CIGARs and were resolved by comparing the ops alone; the counts never depend on the hash.
+ * debug_hash_bits (tests): < 0 or >= 47 the full hash, else that many bits (0: every such run is decided by
+ * the ops alone).
+ * OGE_ERR_ARG (the message names the record): a record inside the region with refID outside [0, n_ref), with a
+ * CIGAR op code above 8, or whose CIGAR does not fit its block_size.  OGE_ERR_LIMIT: n_a + n_b >= 2^32 - 1.
+ * Diff image (want & OGE_COMPARE_DIFF; diff_entries entries, *diff_bytes bytes, any order, little-endian):
+ *   i32 refID, i32 pos, u64 surplus, u32 side (1: set b holds `surplus` more of the element than set a, an
+ *   addition; 0: set a holds more, a deletion), u32 n_ops, u32 ops[n_ops] as in the record (len << 4 | code)
+ * one entry per element whose multiplicities differ.  *d_diff (device) is valid until the next call on ctx.
+ * Stage name for oge_ctx_timing: "compare". */
+typedef struct oge_compare_region {
+    int32_t left_ref, left_pos, right_ref, right_pos;
+} oge_compare_region;
+typedef struct oge_compare_result {
+    uint64_t n_ref, n_other, common, additions, deletions, diff_entries, hard_runs;
+} oge_compare_result;
+enum { OGE_COMPARE_DIFF = 1 };
+/* Records d_recs_x + d_off_x[i] (n_x offsets; the arenas carry 16 bytes of slack behind the last record);
+ * n_ref = the number of contigs of set a's dictionary.  d_diff / diff_bytes may be NULL without OGE_COMPARE_DIFF. */
+int oge_compare_dev(oge_ctx *ctx, const uint8_t *d_recs_a, const uint64_t *d_off_a, uint64_t n_a, const uint8_t *d_recs_b,
+                    const uint64_t *d_off_b, uint64_t n_b, int32_t n_ref, const oge_compare_region *region, uint32_t want,
+                    int debug_hash_bits, oge_compare_result *result, const uint8_t **d_diff, uint64_t *diff_bytes);
+/* Host-buffer form: uploads both sets, compares, copies the image into diff_out (cap bytes; OGE_ERR_LIMIT with
+ * *result and *diff_bytes filled when the image is larger, so a first call with cap 0 sizes the buffer). */
+int oge_compare(oge_ctx *ctx, const uint8_t *recs_a, uint64_t rec_bytes_a, const uint64_t *rec_off_a, uint64_t n_a,
+                const uint8_t *recs_b, uint64_t rec_bytes_b, const uint64_t *rec_off_b, uint64_t n_b, int32_t n_ref,
+                const oge_compare_region *region, uint32_t want, int debug_hash_bits, oge_compare_result *result,
+                uint8_t *diff_out, uint64_t cap, uint64_t *diff_bytes);
+
 /* ---- SAM and FASTQ text of records in HBM (openge view, -F sam|fastq) ----------------------------------
  * The reference's SamWriter::write (util/sam_writer.cpp:90-217) and the single-stream form of
  * FastqWriter::write (util/fastq_writer.cpp:99-100) on the device; DESIGN.md section 21.

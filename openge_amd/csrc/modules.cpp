@@ -1888,4 +1888,201 @@ int coverage_bam_file(ChainContext &cc, const std::string &path, const std::stri
     return 0;
 }
 
+
+// ---- compare -------------------------------------------------------------------------------------------
+namespace {
+
+// one element of the diff image of oge_compare_dev (include/openge_hip.h)
+struct DiffEntry {
+    int32_t refid, pos;
+    uint64_t surplus;
+    uint32_t side;
+    std::vector<uint32_t> ops;  // len << 4 | code
+};
+
+const char kCigarChars[] = "MIDNSHP=X";
+
+// CompareElement::operator< (command_compare.cpp:50-65): the op's length, then its type CHARACTER
+bool diff_less(const DiffEntry &a, const DiffEntry &b) {
+    if (a.refid != b.refid) return a.refid < b.refid;
+    if (a.pos != b.pos) return a.pos < b.pos;
+    if (a.ops.size() != b.ops.size()) return a.ops.size() < b.ops.size();
+    for (size_t i = 0; i < a.ops.size(); ++i) {
+        if ((a.ops[i] >> 4) != (b.ops[i] >> 4)) return (a.ops[i] >> 4) < (b.ops[i] >> 4);
+        const char ta = kCigarChars[a.ops[i] & 0xF], tb = kCigarChars[b.ops[i] & 0xF];
+        if (ta != tb) return ta < tb;
+    }
+    return false;
+}
+
+bool decode_diff(const std::vector<uint8_t> &img, uint64_t entries, std::vector<DiffEntry> &out) {
+    size_t p = 0;
+    out.clear();
+    out.reserve(entries);
+    for (uint64_t k = 0; k < entries; ++k) {
+        if (p + 24 > img.size()) return false;
+        DiffEntry e;
+        e.refid = oge_rd_i32(img.data() + p);
+        e.pos = oge_rd_i32(img.data() + p + 4);
+        e.surplus = (uint64_t)oge_rd_u32(img.data() + p + 8) | ((uint64_t)oge_rd_u32(img.data() + p + 12) << 32);
+        e.side = oge_rd_u32(img.data() + p + 16);
+        const uint32_t nops = oge_rd_u32(img.data() + p + 20);
+        if (p + 24 + 4ull * nops > img.size()) return false;
+        e.ops.resize(nops);
+        for (uint32_t j = 0; j < nops; ++j) e.ops[j] = oge_rd_u32(img.data() + p + 24 + 4 * j);
+        p += 24 + 4ull * nops;
+        out.push_back(std::move(e));
+    }
+    return p == img.size();
+}
+
+// "Add: " / "Del: " + CompareElement::toString (command_compare.cpp:67-71), once per surplus element
+void print_changes(const char *label, uint32_t side, const std::vector<DiffEntry> &d, const std::vector<std::string> &names) {
+    std::string line;
+    for (const DiffEntry &e : d) {
+        if (e.side != side) continue;
+        line = label;
+        line += names[(size_t)e.refid];
+        line += ':';
+        line += std::to_string(e.pos);
+        line += ' ';
+        for (uint32_t op : e.ops) {
+            line += std::to_string(op >> 4);
+            line += kCigarChars[op & 0xF];
+        }
+        line += '\n';
+        for (uint64_t k = 0; k < e.surplus; ++k) fwrite(line.data(), 1, line.size(), stdout);
+    }
+}
+
+struct LoadedReads {
+    ChainContext &cc;
+    ReadBatch b;
+    explicit LoadedReads(ChainContext &c) : cc(c) {}
+    ~LoadedReads() { cc.free_device(b); }
+};
+
+}  // namespace
+
+int compare_files(ChainContext &cc, const std::vector<std::string> &inputs, const std::vector<std::string> &region_strings_in, bool print) {
+    // what is held at once: file 0 and one other file, as records in HBM, and the compare's 44 bytes per record
+    // of keys.  A BAM file is taken as 8 times its size (records and keys), SAM text as 3 times.
+    uint64_t fr = 0, tot = 0, first = 0, largest = 0;
+    if (oge_mem_info(cc.ctx, &fr, &tot)) return cc.fail("compare");
+    for (size_t i = 0; i < inputs.size(); ++i) {
+        struct stat sb;
+        if (stat(inputs[i].c_str(), &sb) != 0) continue;  // the reader reports it
+        const uint64_t est = (uint64_t)sb.st_size * (file_is_sam(inputs[i]) ? 3 : 8);
+        if (i == 0) first = est;
+        else largest = std::max(largest, est);
+    }
+    if (first + largest > tot) {
+        fprintf(stderr, "openge compare: the inputs do not fit in device memory together (about %llu MB needed, %llu MB on the device)\n",
+                (unsigned long long)((first + largest) >> 20), (unsigned long long)(tot >> 20));
+        return -1;
+    }
+    if (inputs.size() < 2) return 0;  // command_compare.cpp:126-196: nothing is compared, nothing printed
+
+    const auto t_start = clk();
+    double t_read = 0, t_compare_ms = 0, t_format = 0;
+    LoadedReads ref(cc);
+    {
+        FileReader reader;
+        reader.addFile(inputs[0]);
+        if (reader.load(cc, ref.b)) return -1;
+    }
+    t_read += sec(t_start, clk());
+    // regions against file 0's dictionary (command_compare.cpp:100-117)
+    std::string names;
+    std::vector<int64_t> lens;
+    std::vector<std::string> contig;
+    for (auto &sq : ref.b.header.sq) {
+        names += sq.name;
+        names.push_back('\0');
+        lens.push_back(sq.length);
+        contig.push_back(sq.name);
+    }
+    std::vector<std::string> region_strings = region_strings_in;
+    std::vector<oge_compare_region> regions;
+    size_t longest = 0;
+    if (!region_strings.empty()) {
+        for (const std::string &rs : region_strings) {
+            oge_filter_opts o;
+            oge_filter_opts_init(&o);
+            if (oge_parse_region(rs.c_str(), names.data(), (int32_t)lens.size(), lens.data(), &o)) {
+                // Filter::ParseRegionString's own message (none when the string itself does not parse), then the command's
+                const std::string why = oge_last_error(nullptr);
+                if (why.rfind("ERROR: could not parse", 0) != 0) fprintf(stderr, "%s\n", why.c_str());
+                fprintf(stderr, "Couldn't understand region string %s. Exiting.\n", rs.c_str());
+                return -1;
+            }
+            regions.push_back({o.ref_id, o.left_pos, o.ref_id, o.right_pos});
+            longest = std::max(longest, rs.size());
+        }
+    } else {
+        region_strings.push_back("");
+        regions.push_back({0, 0, INT_MAX, INT_MAX});
+    }
+    const bool print_file_names = inputs.size() > 2;
+    for (size_t f = 1; f < inputs.size(); ++f) {
+        const auto t0 = clk();
+        LoadedReads other(cc);
+        {
+            FileReader reader;
+            reader.addFile(inputs[f]);
+            if (reader.load(cc, other.b)) return -1;
+        }
+        t_read += sec(t0, clk());
+        // The reference's check (command_compare.cpp:140-144) takes both dictionaries from file 0's reader, so its
+        // warning never appears; here it is real, and shown with -v only: without -v stderr stays the reference's
+        if (cc.verbose && (other.b.header.sq.size() != ref.b.header.sq.size() || other.b.ref_names != ref.b.ref_names))
+            fprintf(stderr, "Sequence dictionaries between %s and %s differ. This may produce inconsistent results.\n", inputs[0].c_str(),
+                    inputs[f].c_str());
+        if (print_file_names) {
+            fflush(stdout);
+            fprintf(stderr, "%s:\n", inputs[f].c_str());
+        }
+        for (size_t r = 0; r < regions.size(); ++r) {
+            oge_compare_result res;
+            const uint8_t *d_diff = nullptr;
+            uint64_t diff_bytes = 0;
+            std::vector<uint8_t> img;
+            int rc = oge_compare_dev(cc.ctx, ref.b.d_recs, ref.b.d_offs, ref.b.n, other.b.d_recs, other.b.d_offs, other.b.n,
+                                     (int32_t)contig.size(), &regions[r], print ? OGE_COMPARE_DIFF : 0, -1, &res, &d_diff, &diff_bytes);
+            if (!rc && diff_bytes) {
+                img.resize(diff_bytes);
+                rc = oge_memcpy(cc.ctx, img.data(), d_diff, diff_bytes, 2);
+            }
+            if (rc) return cc.fail("compare");
+            double ms = 0;
+            oge_ctx_timing(cc.ctx, "compare", &ms);
+            t_compare_ms += ms;
+            const auto tf = clk();
+            if (print) {
+                std::vector<DiffEntry> d;
+                if (!decode_diff(img, res.diff_entries, d)) {
+                    fprintf(stderr, "openge compare: malformed diff image\n");
+                    return -1;
+                }
+                std::sort(d.begin(), d.end(), diff_less);
+                print_changes("Add: ", 1, d, contig);
+                print_changes("Del: ", 0, d, contig);
+            }
+            if (res.additions || res.deletions)
+                printf("%s%*s\t%8llu added\t%8llu removed\n", print_file_names ? "   " : "", (int)longest, region_strings[r].c_str(),
+                       (unsigned long long)res.additions, (unsigned long long)res.deletions);
+            t_format += sec(tf, clk());
+        }
+    }
+    const bool ok = fflush(stdout) == 0 && !ferror(stdout);
+    if (cc.verbose)
+        fprintf(stderr, "[openge] compare: read + inflate %.3f s, compare %.1f ms on the device, format %.3f s, total %.3f s\n", t_read,
+                t_compare_ms, t_format, sec(t_start, clk()));
+    if (!ok) {
+        fprintf(stderr, "openge: error writing to stdout\n");
+        return -1;
+    }
+    return 0;
+}
+
 }  // namespace oge

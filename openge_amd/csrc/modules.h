@@ -112,6 +112,11 @@ public:
     void addFile(const std::string &f) { files_.push_back(f); }
     void addFiles(const std::vector<std::string> &f) { files_.insert(files_.end(), f.begin(), f.end()); }
     void setLoadStringData(bool) {}  // the record arena always keeps the full record bytes
+    // outside a chain (compare_files): this reader's files into b, the records resident in HBM
+    int load(ChainContext &cc, ReadBatch &b) {
+        const int rc = runInternal(cc, b);
+        return rc ? rc : cc.to_device(b);
+    }
 protected:
     int runInternal(ChainContext &cc, ReadBatch &b) override;
     // One BGZF file straight into HBM: inflate + record walk on the GPU (returns 1 when the host
@@ -250,5 +255,11 @@ int index_bam_file(ChainContext &cc, const std::string &path, const std::string 
 int stats_bam_file(ChainContext &cc, const std::string &path, bool inserts, bool lengths);
 int count_bam_file(ChainContext &cc, const std::string &path);
 int coverage_bam_file(ChainContext &cc, const std::string &path, const std::string &out, int binsize, bool omit_uncovered);
+
+// `openge compare [-r REGION]... [-p] ref.bam other.bam [more...]` (commands/command_compare.cpp): every input
+// through a FileReader into its own batch in HBM, file 0 resident while the others come and go; the regions
+// parsed against file 0's dictionary; one oge_compare_dev call per (file, region); the reference's text formatted
+// on the host, the file names on stderr, everything else on stdout
+int compare_files(ChainContext &cc, const std::vector<std::string> &inputs, const std::vector<std::string> &regions, bool print);
 
 }  // namespace oge

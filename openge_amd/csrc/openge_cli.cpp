@@ -7,6 +7,8 @@
 // `index`, `stats`, `count` and `coverage` are one whole-file device call each (index_bam_file,
 // stats_bam_file, count_bam_file, coverage_bam_file in modules.cpp; commands/command_stats.cpp,
 // command_count.cpp, command_coverage.cpp for the last three).
+// `compare` loads every input into HBM and takes the multiset difference of the read placements there
+// (compare_files in modules.cpp, csrc/compare.hip; commands/command_compare.cpp).
 //
 // Deliberate differences: view -B/-E cuts QUAL to the window of SEQ; the reference cuts the
 // qualities of the already shortened read a second time (algorithms/filter.cpp:188-189), which leaves fewer
@@ -67,6 +69,7 @@ const Opt kIndex[] = {{"o", "out", true}};
 const Opt kStats[] = {{"I", "inserts", false}, {"L", "lengths", false}};
 const Opt kCoverage[] = {{"o", "out", true}, {"b", "binsize", true}, {"", "omituncoveredbases", false},
                          {"V", "verifymapping", false}, {"S", "strict", false}};
+const Opt kCompare[] = {{"r", "region", true}, {"p", "print", false}};
 const Opt kRealign[] = {{"o", "out", true}, {"R", "reference", true}, {"L", "intervals", true}};
 
 struct Parsed {
@@ -127,7 +130,7 @@ bool parse(int argc, const char **argv, const std::vector<Opt> &opts, Parsed &p)
 
 void usage_top() {
     fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, view, index, stats, count, coverage,\n"
-                    "          version\n"
+                    "          compare, version\n"
                     "\n    Inputs are BAM files or SAM text (first byte '@'; also on stdin, and mixed with BAM files); SAM is parsed\n"
                     "    on the GPU.  index takes BAM only.\n"
                     "\n    openge view [-o out] [-n N] [-q MAPQ] [-l LEN] [-r REGION] [-B N] [-E N] in.bam|in.sam\n"
@@ -143,6 +146,10 @@ void usage_top() {
                     "    openge count in.bam|in.sam          the number of reads\n"
                     "    openge coverage [-o out.tsv] [-b N] [--omituncoveredbases] in.bam|in.sam\n"
                     "                                        depth per bin of N bases (default 100); one file, one GPU\n"
+                    "    openge compare [-r REGION]... [-p] ref.bam|ref.sam other.bam|other.sam [more...]\n"
+                    "                                        read placements (contig, position, CIGAR) of every later file that\n"
+                    "                                        the first one lacks (added) or has more of (removed), per region\n"
+                    "                                        (reads that START in it); -p prints each one; one GPU, no stdin\n"
                     "\nGPU options (every command):\n"
                     "    --device N              first GPU\n"
                     "    --gpus G                ranks over G GPUs\n"
@@ -176,6 +183,7 @@ int main(int argc, const char **argv) {
     else if (cmd == "stats") opts.insert(opts.end(), std::begin(kStats), std::end(kStats));
     else if (cmd == "count") ;  // no options of its own (commands/command_count.cpp)
     else if (cmd == "coverage") opts.insert(opts.end(), std::begin(kCoverage), std::end(kCoverage));
+    else if (cmd == "compare") opts.insert(opts.end(), std::begin(kCompare), std::end(kCompare));
     else {
         fprintf(stderr, "Unknown command %s.\n", argv[1]);
         return -1;
@@ -292,6 +300,17 @@ int main(int argc, const char **argv) {
             return -1;
         }
     }
+    if (cmd == "compare") {  // refused before anything is read
+        for (auto &in : p.inputs)
+            if (in == "stdin" || in == "-") {
+                fprintf(stderr, "openge compare: stdin is not provided as an input (every file is read on its own, the first one for every other)\n");
+                return -1;
+            }
+        if (cc.gpus > 1) {
+            fprintf(stderr, "openge compare: --gpus is not provided\n");
+            return -1;
+        }
+    }
     timeval t0;
     gettimeofday(&t0, nullptr);
     // one input file on one GPU: its bytes come off the disk / page cache while HIP initialises
@@ -307,6 +326,11 @@ int main(int argc, const char **argv) {
     }
     if (cmd == "index") {
         const int r = index_bam_file(cc, p.inputs[0], p.get("out", p.inputs[0] + ".bai"));
+        oge_ctx_destroy(cc.ctx);
+        return r;
+    }
+    if (cmd == "compare") {
+        const int r = compare_files(cc, p.inputs, p.count("region") ? p.vm["region"] : std::vector<std::string>(), p.count("print"));
         oge_ctx_destroy(cc.ctx);
         return r;
     }

@@ -60,6 +60,32 @@ class BamStats(C.Structure):
 
 
 STATS_INSERTS, STATS_LENGTHS = 1, 2
+
+
+class CompareRegion(C.Structure):
+    """Mirror of oge_compare_region: start positions left..right on contigs left_ref..right_ref, all inclusive."""
+    _fields_ = [(k, C.c_int32) for k in ("left_ref", "left_pos", "right_ref", "right_pos")]
+
+
+class CompareResult(C.Structure):
+    """Mirror of oge_compare_result (include/openge_hip.h)."""
+    FIELDS = ("n_ref", "n_other", "common", "additions", "deletions", "diff_entries", "hard_runs")
+    _fields_ = [(k, C.c_uint64) for k in FIELDS]
+
+
+COMPARE_DIFF = 1
+COMPARE_ALL = (0, 0, 2**31 - 1, 2**31 - 1)  # the region of `openge compare` without -r
+
+
+def decode_compare_diff(image: bytes) -> list[tuple]:
+    """The diff image of oge_compare(_dev) -> [(side, refID, pos, surplus, (op word, ...))], in image order."""
+    import struct
+    out, p = [], 0
+    while p < len(image):
+        refid, pos, surplus, side, nops = struct.unpack_from("<iiQII", image, p)
+        out.append((side, refid, pos, surplus, struct.unpack_from(f"<{nops}I", image, p + 24)))
+        p += 24 + 4 * nops
+    return out
 TEXT_SAM, TEXT_FASTQ = 0, 1
 
 
@@ -310,6 +336,8 @@ def lib() -> C.CDLL:
         "oge_ctx_last_bai": (C.c_int, [vp, C.POINTER(vp), C.POINTER(u64)]),
         "oge_stats_dev": (C.c_int, [vp, vp, vp, u64, u32, vp, C.POINTER(vp), C.POINTER(vp)]),
         "oge_stats": (C.c_int, [vp, vp, u64, vp, u64, u32, vp, vp, vp, u64]),
+        "oge_compare_dev": (C.c_int, [vp, vp, vp, u64, vp, vp, u64, i32, vp, u32, C.c_int, vp, C.POINTER(vp), C.POINTER(u64)]),
+        "oge_compare": (C.c_int, [vp, vp, u64, vp, u64, vp, u64, vp, u64, i32, vp, u32, C.c_int, vp, vp, u64, C.POINTER(u64)]),
         "oge_coverage_layout": (C.c_int, [i32, vp, i32, vp]),
         "oge_coverage_dev": (C.c_int, [vp, vp, vp, u64, i32, vp, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(i32)]),
         "oge_coverage": (C.c_int, [vp, vp, u64, vp, u64, i32, vp, i32, vp, u64, C.POINTER(u64), C.POINTER(i32)]),
@@ -702,6 +730,37 @@ class Context:
         out = self._stats_dict(st, C.c_void_p(), C.c_void_p(), False)
         if lengths:
             out["lengths"] = (ln[:st.n_lengths], ct[:st.n_lengths])
+        return out
+
+    # ---- compare (csrc/compare.hip)
+    def compare_dev(self, d_recs_a, d_off_a, n_a: int, d_recs_b, d_off_b, n_b: int, n_ref: int, region=COMPARE_ALL,
+                    diff: bool = False, hash_bits: int = -1) -> dict:
+        """oge_compare_dev on two device record sets (set a is the reference set) -> the counts of
+        oge_compare_result and, with diff, `diff` = the decoded image (decode_compare_diff)."""
+        rg, res, dd, nb = CompareRegion(*region), CompareResult(), C.c_void_p(), C.c_uint64()
+        check(lib().oge_compare_dev(self.h, d_recs_a, d_off_a, n_a, d_recs_b, d_off_b, n_b, n_ref, C.byref(rg),
+                                    COMPARE_DIFF if diff else 0, hash_bits, C.byref(res), C.byref(dd), C.byref(nb)), self.h)
+        out = {k: getattr(res, k) for k in CompareResult.FIELDS}
+        if diff:
+            out["diff"] = decode_compare_diff(self._fetch(dd.value or 0, nb.value))
+        return out
+
+    def compare(self, recs_a: np.ndarray, offs_a: np.ndarray, n_a: int, recs_b: np.ndarray, offs_b: np.ndarray, n_b: int, n_ref: int,
+                region=COMPARE_ALL, diff: bool = False, hash_bits: int = -1) -> dict:
+        """oge_compare: the same from host buffers (a sizing call, then the call that copies the image)."""
+        offs_a, offs_b = np.ascontiguousarray(offs_a, dtype=np.uint64), np.ascontiguousarray(offs_b, dtype=np.uint64)
+        rg, res, nb = CompareRegion(*region), CompareResult(), C.c_uint64()
+        args = (self.h, _ptr(recs_a), recs_a.nbytes, _ptr(offs_a), n_a, _ptr(recs_b), recs_b.nbytes, _ptr(offs_b),
+                n_b, n_ref, C.byref(rg), COMPARE_DIFF if diff else 0, hash_bits, C.byref(res))
+        rc = lib().oge_compare(*args, None, 0, C.byref(nb))
+        if not (rc == -3 and diff and nb.value):  # OGE_ERR_LIMIT with the size: the sizing call
+            check(rc, self.h)
+        buf = np.empty(max(nb.value, 1), np.uint8)
+        if rc:
+            check(lib().oge_compare(*args, _ptr(buf), len(buf), C.byref(nb)), self.h)
+        out = {k: getattr(res, k) for k in CompareResult.FIELDS}
+        if diff:
+            out["diff"] = decode_compare_diff(buf[:nb.value].tobytes())
         return out
 
     # ---- SAM / FASTQ text (csrc/sam.hip)
