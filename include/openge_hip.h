@@ -443,6 +443,14 @@ int oge_bgzf_index_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint64
  * checks every payload's CRC-32.  Fails with OGE_ERR_IO on corrupt data. */
 int oge_bgzf_inflate_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const uint64_t *d_d0, const uint64_t *d_d1,
                          const uint64_t *d_uoff, const uint32_t *d_crc, uint64_t nblk, uint8_t *d_out);
+/* Host, no device: how the inflate cuts nblk blocks into phase-1 launches over `lanes` resident decoder lanes
+ * when the workspace holds `budget` blocks and a launch takes at most max_per_lane blocks per lane (0: the
+ * build's value).  Every chunk is R * lanes blocks, R = clamp(budget / lanes, 1, max_per_lane), and the last
+ * takes the remainder, so the launches run ceil(nblk / lanes) rounds for any budget; balanced != 0: the equal
+ * chunks OGE_INFL_PLAN=balanced selects.  Returns the chunk count; the first min(count, cap) sizes go to sizes
+ * (may be NULL).  The context counters infl_chunks, infl_rounds and infl_lanes report what a call ran. */
+uint64_t oge_infl_plan(uint64_t nblk, uint64_t lanes, uint64_t budget, uint64_t max_per_lane, int balanced,
+                       uint64_t *sizes, uint64_t cap);
 /* Host-buffer form: the whole BGZF stream z -> out (out_cap >= payload total). */
 int oge_bgzf_inflate(oge_ctx *ctx, const uint8_t *z, uint64_t zbytes, uint8_t *out, uint64_t out_cap,
                      uint64_t *out_bytes);

@@ -37,6 +37,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
@@ -1638,7 +1639,46 @@ __global__ void __launch_bounds__(kT2) k_infl_lz(uint8_t *__restrict__ out, cons
     }
 }
 
+// How nblk blocks are cut into phase-1 launches (pure host arithmetic).  The lanes of a launch stay in
+// lockstep (equal payloads, similar content), so a launch over nb blocks runs ceil(nb / lanes) ROUNDS of one
+// block's iterations each; a round in which few lanes hold a block is cheaper than a full one but not free, and
+// every launch adds its own ramp and tail (*Phase 1's rounds*: about 15 ms each at 300M reads).
+// budget: the blocks whose bitmaps and lists fit the memory set aside; max_per_lane: the most blocks per lane
+// in one launch.
+//   whole rounds: every chunk is R * lanes blocks, R = clamp(budget / lanes, 1, max_per_lane), the last takes the
+//     remainder: ceil(nblk / lanes) rounds in all for any budget -- memory changes the launches, not the rounds.
+//   balanced (the plan before; OGE_INFL_PLAN=balanced): the fewest chunks of at most max(lanes, min(budget,
+//     max_per_lane * lanes)) blocks, of equal size -- 6.64 blocks per lane as 4 x 1.66 run 8 rounds, not 7.
+std::vector<uint64_t> infl_plan(uint64_t nblk, uint64_t lanes, uint64_t budget, uint64_t max_per_lane, bool balanced) {
+    std::vector<uint64_t> sizes;
+    lanes = std::max<uint64_t>(lanes, 1);
+    max_per_lane = std::max<uint64_t>(max_per_lane, 1);
+    uint64_t chunk;
+    if (balanced) {
+        const uint64_t most = std::max(lanes, std::min(max_per_lane * lanes, budget));
+        const uint64_t nchunks = std::max<uint64_t>(1, (nblk + most - 1) / most);
+        chunk = std::max<uint64_t>(1, (nblk + nchunks - 1) / nchunks);
+    } else {
+        chunk = std::min(std::max<uint64_t>(budget / lanes, 1), max_per_lane) * lanes;
+    }
+    for (uint64_t b0 = 0; b0 < nblk; b0 += chunk) sizes.push_back(std::min(chunk, nblk - b0));
+    return sizes;
+}
+
+// a per-call knob of the tests and the A/B runs: the variable's number, or dflt
+uint64_t env_u64(const char *name, uint64_t dflt) {
+    const char *e = getenv(name);
+    return e && *e ? strtoull(e, nullptr, 10) : dflt;
+}
+
 }  // namespace
+
+extern "C" uint64_t oge_infl_plan(uint64_t nblk, uint64_t lanes, uint64_t budget, uint64_t max_per_lane, int balanced,
+                                  uint64_t *sizes, uint64_t cap) {
+    const std::vector<uint64_t> v = infl_plan(nblk, lanes, budget, max_per_lane ? max_per_lane : kChunkLanes, balanced != 0);
+    for (uint64_t i = 0; i < v.size() && i < cap && sizes; ++i) sizes[i] = v[i];
+    return v.size();
+}
 
 // Inflate indexed blocks [0, nblk) with the lane decoder; err as in oge_bgzf_inflate_dev (err[0] bits,
 // err[1] first failing block).  zpow: the CRC zero operators (device).
@@ -1648,7 +1688,11 @@ int oge_inflate_lanes(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const u
     const int ncu = ctx->cu_count();
     // persistent lanes (the 12 resident waves per CU) take blocks from a queue; a chunk is at most
     // kChunkLanes blocks per lane, and no more than a quarter of the free device memory holds bitmaps and
-    // lists for (17.3 KiB per block), at least one block per lane.  With kStreams > 1, chunks alternate
+    // lists for (17.3 KiB per block), at least one block per lane; infl_plan cuts the blocks into chunks of
+    // whole rounds of the lanes (the queue still evens out blocks of unequal decode length inside a chunk).
+    // OGE_INFL_PLAN=balanced selects the equal chunks of before; OGE_INFL_WGS caps the phase-1 workgroups (and
+    // so the lanes) and OGE_INFL_BUDGET gives the budget in blocks, so that tests see rounds at small sizes:
+    // all three are read per call.  With kStreams > 1, chunks alternate
     // over that many streams with a buffer set each, so one chunk's phase-1 drain and phase 2 can overlap
     // the next chunk.  Measured (r04): standalone at 100M reads (435k blocks) three chunks of one block
     // per lane on two streams beat one chunk on one stream (209-218 vs 225 ms) and at 200M two chunks of
@@ -1656,15 +1700,39 @@ int oge_inflate_lanes(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const u
     // one stream with chunks of four blocks per lane is fastest: 649 ms against 695 (two streams, one
     // per lane), 715 (two, two) and 728 (two, four): concurrent phase-1 launches on two streams share the
     // CUs and the L2 and both finish late.  So one stream by default (a 14 GB workspace at 300M).
-    const uint64_t lanes = (uint64_t)ncu * 4 * kWps * 64;
+    const uint64_t wg_cap = env_u64("OGE_INFL_WGS", 0);
+    const uint64_t lanes = std::min<uint64_t>((uint64_t)ncu * 4 * kWps, wg_cap ? wg_cap : ~0ull) * 64;
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
     constexpr uint64_t kPerBlk = kBmStride * 8 + kXTab + kPrep + 4;  // bitmaps + translation lists + prepared tables
     constexpr int S = kStreams;
-    const uint64_t budget =
-        std::max<uint64_t>(lanes, std::min<uint64_t>(kChunkLanes * lanes, (uint64_t)(fr / 4) / (S * kPerBlk)));
-    const uint64_t nchunks = std::max<uint64_t>(1, (nblk + budget - 1) / budget);
-    const uint64_t chunk = std::max<uint64_t>(1, (nblk + nchunks - 1) / nchunks);
+    const char *pl = getenv("OGE_INFL_PLAN");  // an unknown word is an error, not the default
+    if (pl && *pl && strcmp(pl, "whole") && strcmp(pl, "balanced"))
+        return oge_fail(ctx, OGE_ERR_ARG, (std::string("OGE_INFL_PLAN=") + pl + " (whole or balanced)").c_str());
+    const bool balanced = pl && !strcmp(pl, "balanced");
+    // OGE_INFL_PREP=0: no header pre-pass (phase 1 parses every header itself; the A/B switch)
+    const char *pe = getenv("OGE_INFL_PREP");
+    const bool use_prep = !(pe && *pe == '0');
+    // The blocks the per-block workspaces this context already holds have room for cost no more memory: a
+    // context's later calls keep the chunk of its first one, although the free memory they see is smaller by
+    // that very workspace (the 300M chain: 310k blocks' worth free in a steady step, 786k held -- one-round
+    // launches otherwise, each with its own ramp and tail).  The plan of before looks at the free memory only.
+    uint64_t held = ~0ull;
+    for (int k = 0; k < S && !balanced; ++k) {
+        auto room = [&](const char *name, uint64_t per) {
+            const auto it = ctx->bufs.find(name + std::to_string(k));
+            return it == ctx->bufs.end() || !it->second.p ? 0 : (uint64_t)it->second.cap / per;
+        };
+        held = std::min({held, room("infl_bitmap", kBmStride * 8), room("infl_xtab", kXTab)});
+        if (use_prep) held = std::min({held, room("infl_prep", kPrep), room("infl_pmeta", 4)});
+    }
+    if (balanced) held = 0;
+    const uint64_t budget = env_u64("OGE_INFL_BUDGET", std::max<uint64_t>((uint64_t)(fr / 4) / (S * kPerBlk), held));
+    // Tried and not kept (r08): the part of the last chunk beyond its whole rounds as a launch of its own on
+    // fewer, full waves -- 100M / 95M reads (2.21 / 2.10 blocks per lane) infl_huff 84.0 -> 101.8 / 79.8 -> 99.9 ms:
+    // a launch of a tenth of the lanes still costs one block's serial decode time and its own ramp and tail.
+    const std::vector<uint64_t> plan = infl_plan(nblk, lanes, budget, kChunkLanes, balanced);
+    const uint64_t chunk = plan.empty() ? 1 : plan[0];  // the largest: the workspaces are sized for it
     const uint64_t wgs = std::min<uint64_t>((chunk + 63) / 64, lanes / 64);
     struct Set {
         uint64_t *bitmap;
@@ -1673,9 +1741,6 @@ int oge_inflate_lanes(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const u
         unsigned long long *next;
         hipStream_t st;
     } B[S];
-    // OGE_INFL_PREP=0: no header pre-pass (phase 1 parses every header itself; the A/B switch)
-    const char *pe = getenv("OGE_INFL_PREP");
-    const bool use_prep = !(pe && *pe == '0');
     for (int k = 0; k < S; ++k) {
         const std::string x = std::to_string(k);
         B[k].bitmap = (uint64_t *)ctx->ws(("infl_bitmap" + x).c_str(), chunk * kBmStride * 8);
@@ -1702,10 +1767,12 @@ int oge_inflate_lanes(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const u
         OGE_HIP_TRY(ctx, hipEventRecord(ev[S], ctx->stream));
         for (int k = 0; k < S; ++k) OGE_HIP_TRY(ctx, hipStreamWaitEvent(B[k].st, ev[S], 0));
     }
-    uint64_t k = 0;
-    for (uint64_t b0 = 0; b0 < nblk; b0 += chunk, ++k) {
-        const uint64_t nb = std::min(chunk, nblk - b0);
+    uint64_t k = 0, rounds = 0, b0 = 0;
+    for (; k < plan.size(); b0 += plan[k], ++k) {
+        const uint64_t nb = plan[k];
         const uint32_t g1 = (uint32_t)std::min<uint64_t>((nb + 63) / 64, wgs);
+        const uint64_t on = std::min<uint64_t>(lanes, 64ull * g1);
+        rounds += (nb + on - 1) / on;
         const Set &u = B[k % S];
         OGE_HIP_TRY(ctx, hipMemsetAsync(u.next, 0, 8, u.st));
         // phase 1 stores only words with bits, so the bitmaps must start clear: phase 2 clears every word it
@@ -1740,6 +1807,14 @@ int oge_inflate_lanes(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const u
         stage.end();
         if (S == 1) ctx->infl_clean_ptr = u.bitmap, ctx->infl_clean_bytes = ctx->infl_clean_next;
     }
+    ctx->counters["infl_chunks"] += k;
+    ctx->counters["infl_rounds"] += rounds;
+    ctx->counters["infl_lanes"] = lanes;
+    static const bool tr = getenv("OGE_TRACE_INFL") != nullptr;
+    if (tr)
+        fprintf(stderr, "[oge infl] %llu blocks, %llu lanes, budget %llu, %s: %llu chunks of %llu, %llu rounds\n",
+                (unsigned long long)nblk, (unsigned long long)lanes, (unsigned long long)budget, balanced ? "balanced" : "whole",
+                (unsigned long long)k, (unsigned long long)chunk, (unsigned long long)rounds);
     if (S > 1) {  // the context stream waits for every chunk
         for (int j = 0; j < S; ++j) {
             OGE_HIP_TRY(ctx, hipEventRecord(ev[j], B[j].st));

@@ -322,6 +322,7 @@ def lib() -> C.CDLL:
         "oge_bgzf_index": (C.c_int, [vp, u64, vp, vp, vp, vp, u64, C.POINTER(u64)]),
         "oge_bgzf_inflate_dev": (C.c_int, [vp, vp, u64, vp, vp, vp, vp, u64, vp]),
         "oge_bgzf_inflate": (C.c_int, [vp, vp, u64, vp, u64, C.POINTER(u64)]),
+        "oge_infl_plan": (u64, [u64, u64, u64, u64, C.c_int, vp, u64]),
         "oge_bam_record_offsets_dev": (C.c_int, [vp, vp, u64, u64, i32, vp, u64, C.POINTER(u64)]),
         "oge_drop_flagged_dev": (C.c_int, [vp, vp, vp, u64, C.c_uint16, vp, vp, C.POINTER(u64)]),
         "oge_filter_opts_init": (None, [vp]),
@@ -384,6 +385,15 @@ def parse_region(region: str, refs: list[tuple[str, int]], opts: FilterOpts | No
     lens = np.array([ln for _, ln in refs] or [0], dtype=np.int64)
     check(lib().oge_parse_region(region.encode(), names, len(refs), _ptr(lens), C.byref(o)))
     return o
+
+
+def infl_plan(nblk: int, lanes: int, budget: int, max_per_lane: int = 0, balanced: bool = False) -> list[int]:
+    """oge_infl_plan: the sizes of the phase-1 launches the inflate cuts nblk blocks into (host arithmetic, no
+    device); max_per_lane 0 is the build's value."""
+    n = int(lib().oge_infl_plan(nblk, lanes, budget, max_per_lane, int(balanced), None, 0))
+    sizes = np.zeros(max(n, 1), dtype=np.uint64)
+    lib().oge_infl_plan(nblk, lanes, budget, max_per_lane, int(balanced), _ptr(sizes), n)
+    return [int(x) for x in sizes[:n]]
 
 
 def exported_symbols() -> list[str]:
