@@ -494,6 +494,53 @@ int oge_bam_index_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const u
  * built; OGE_ERR_ARG when there is none. */
 int oge_ctx_last_bai(oge_ctx *ctx, const uint8_t **d_bai, uint64_t *bai_bytes);
 
+/* ---- reading a BAM index: the ranges of the file that a list of regions needs ------
+ * oge_bai_open takes the bytes of any valid .bai (bins in any order, n_no_coor present or not; not only this
+ * project's canonical form), checks every length in it against the image on the host and puts it into HBM with
+ * a sorted bin directory.  OGE_ERR_ARG, before anything is launched or allocated on the device: no magic, a
+ * truncated image, bytes behind the last section, a bin number above 37450, n_ref != n_ref_expected (the BAM
+ * header's; < 0: not compared).  The handle belongs to ctx and is released with oge_bai_close (NULL allowed). */
+typedef struct oge_bai oge_bai;
+int oge_bai_open(oge_ctx *ctx, const uint8_t *bai, uint64_t bytes, int32_t n_ref_expected, oge_bai **out);
+void oge_bai_close(oge_bai *bai);
+/* The virtual-offset ranges that hold every record overlapping one of the regions (a host array; oge_region is
+ * declared with the Filter below).  Region g asks for the reference positions [max(0, left_pos - widen),
+ * min(right_pos + 1, 2^29)) of ref_id: the chunks of the bins of that interval (reg2bins, SAM v1 section 5.3), each
+ * cut at the linear index entry of the interval's first 16 Ki window.  A region that is empty, whose ref_id is
+ * outside [0, n_ref), whose first window lies past the reference's last one or whose reference has no bins asks
+ * for nothing.  widen >= 0 reaches back for records that start before left_pos (their l_seq is not what the index
+ * was built from).
+ * Result: the UNION of all those half-open intervals [beg, end) of virtual offsets -- overlapping and touching
+ * ones joined, empty ones dropped, ascending -- as *n_ranges pairs (beg, end) at *d_ranges (device), valid until
+ * the context's next query; NULL and 0 when there is none.  Counter "baiq_ranges" = *n_ranges.  Everything else
+ * the call allocates is released before it returns.  OGE_ERR_LIMIT: more than 2^23 regions, or 2^32 - 2 ranges
+ * before the merge.  Stage name for oge_ctx_timing: "bai_query". */
+struct oge_region;
+int oge_bai_query_dev(oge_ctx *ctx, const oge_bai *bai, const struct oge_region *regions, uint64_t n_regions, int32_t widen,
+                      const uint64_t **d_ranges, uint64_t *n_ranges);
+/* Host-buffer form: the pairs into out (cap pairs; OGE_ERR_LIMIT with *n_ranges set when there are more). */
+int oge_bai_query(oge_ctx *ctx, const oge_bai *bai, const struct oge_region *regions, uint64_t n_regions, int32_t widen,
+                  uint64_t *out, uint64_t cap, uint64_t *n_ranges);
+/* The records of the ranges a query returned, decoded from the parts of the file that hold them.  d_z (device,
+ * 4-byte aligned, zbytes bytes) holds n_spans spans of the file back to back, each a run of whole BGZF blocks,
+ * so d_z is a BGZF stream of its own: span s is the file's bytes [span_file[s], span_file[s] + span_z[s + 1] -
+ * span_z[s]) at d_z + span_z[s] (host arrays; span_z has n_spans + 1 entries, span_z[0] = 0, span_z[n_spans] =
+ * zbytes; the spans ascend in the file and do not overlap).  d_ranges: n_ranges (beg, end) pairs as
+ * oge_bai_query_dev returns them (device), each beginning and ending in a block of the spans; an end may be the
+ * first byte behind its span.  The spans are indexed and inflated with one block table, every range's payload
+ * bytes are copied into one arena back to back (the chunks of an index are whole records, so the arena is a
+ * record stream) and the record walk of oge_bam_record_offsets_dev runs over it once.
+ * *d_recs / *d_off (*n + 1 offsets from *d_recs, *rec_bytes bytes of records, 64 zero bytes of slack behind them)
+ * are the caller's, to be released with oge_dev_free (NULL when there is no record); everything else the call
+ * allocates is released before it returns.  OGE_ERR_ARG: a range that does not begin at
+ * the first byte of a block of the spans or reaches past its payload, spans that are not whole blocks;
+ * OGE_ERR_IO: corrupt blocks, or a packed stream that the walk does not consume exactly (a refID outside
+ * [-1, n_ref) included).  Counter "baiq_blocks": the blocks inflated.  Stage name for oge_ctx_timing:
+ * "ranges_pack" (positions, scan and copy); the inflate and the walk report under their own names. */
+int oge_bam_decode_ranges_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const uint64_t *span_z,
+                              const uint64_t *span_file, uint64_t n_spans, const uint64_t *d_ranges, uint64_t n_ranges,
+                              int32_t n_ref, uint8_t **d_recs, uint64_t **d_off, uint64_t *n, uint64_t *rec_bytes);
+
 /* ---- stats, count and coverage of records in HBM (openge stats / count / coverage) ------------------
  * The reference's Statistics and MeasureCoverage modules (algorithms/statistics.cpp,
  * algorithms/measure_coverage.cpp) as reductions on the device; DESIGN.md section 20.  len = l_seq.
@@ -739,6 +786,23 @@ int oge_parse_region(const char *region, const char *ref_names, int32_t n_ref, c
 /* Copy the records the filter keeps, in input order, to d_out / d_out_off (*n_out records). */
 int oge_filter_records_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n,
                            const oge_filter_opts *o, uint8_t *d_out, uint64_t *d_out_off, uint64_t *n_out);
+/* One region of a region list (view / mergesort -L): the ref_id, left_pos and right_pos of oge_filter_opts. */
+typedef struct oge_region {
+    int32_t ref_id, left_pos, right_pos;
+} oge_region;
+/* The same compaction against a list of regions (a host array, n_regions >= 1; OGE_ERR_ARG otherwise): a
+ * record is kept when the predicate above holds without its region part and
+ *   refID == ref_id && pos + len >= left_pos && pos <= right_pos
+ * holds for AT LEAST ONE region; every kept record is written once, in input order, at most count_limit of
+ * them.  has_region and the region fields of `o` are not read.  The regions are sorted by (ref_id, left_pos)
+ * on the device and given the running maximum of right_pos within their ref_id; a record then needs one
+ * binary search (the last region with left_pos <= pos + len) and one compare (that maximum >= pos), whatever
+ * n_regions is and however the regions overlap.  With one region the output equals oge_filter_records_dev's
+ * byte for byte.  All scratch sized by n_regions is released before the call returns.  Stage names for
+ * oge_ctx_timing: "filter_regions" (sort and maxima), "filter" (the predicate). */
+int oge_filter_regions_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n,
+                           const oge_filter_opts *o, const oge_region *regions, uint64_t n_regions, uint8_t *d_out,
+                           uint64_t *d_out_off, uint64_t *n_out);
 /* Sort::ByName (util/bamtools/Sort.h:67-90) as ReadSorter uses it for SORT_QUERYNAME
  * (algorithms/read_sorter.cpp:202-203): read names compared bytewise (std::string <); records
  * with equal names keep input order (the reference's std::sort leaves their order

@@ -74,3 +74,7 @@ OGE_HD int32_t oge_rec_end(const uint8_t *rec) {
 OGE_HD uint16_t oge_rec_bin(const uint8_t *rec) {
     return (uint16_t)oge_reg2bin(oge_rd_i32(rec + OGE_OFF_POS), oge_rec_end(rec));
 }
+
+// The largest block_size the record walks admit (BamDeserializer::read rejects more, util/bam_deserializer.h:160);
+// a record's l_seq is below it, which is what FileReader's index query widens its regions by (modules.h).
+#define OGE_MAX_BLOCK_SIZE 10000

@@ -39,6 +39,10 @@ public:
         else cap_ = bytes;
         return rc;
     }
+    void adopt(void *p, uint64_t bytes) {  // takes a buffer the C ABI handed to its caller; frees what it held
+        reset();
+        p_ = p, cap_ = bytes;
+    }
     int need(uint64_t bytes) { return bytes <= cap_ ? 0 : alloc(bytes); }  // grows only
     template <class T>
     T *as() const { return (T *)p_; }

@@ -38,7 +38,7 @@ __device__ __forceinline__ uint32_t rd32u(const uint8_t *p) {
 __device__ bool plausible(const uint8_t *d, uint64_t s, uint64_t n, int32_t n_ref) {
     if (s + 36 > n) return false;
     const uint32_t bs = rd32u(d + s);
-    if (bs < 32 || bs > 10000 || s + 4 + bs > n) return false;
+    if (bs < 32 || bs > OGE_MAX_BLOCK_SIZE || s + 4 + bs > n) return false;
     const int32_t ref = (int32_t)rd32u(d + s + 4), mref = (int32_t)rd32u(d + s + 24);
     if (ref < -1 || ref >= n_ref || mref < -1 || mref >= n_ref) return false;
     const uint32_t lname = d[s + 12], nc = d[s + 16] | (d[s + 17] << 8), lseq = rd32u(d + s + 20);
@@ -107,7 +107,7 @@ __device__ __forceinline__ uint64_t walk_chunk(const uint8_t *__restrict__ d, ui
     while (q < end) {
         if (q + 4 > n) break;
         const uint32_t bs = rd32u(d + q);
-        if (bs < 32 || bs > 10000 || q + 4 + bs > n) break;
+        if (bs < 32 || bs > OGE_MAX_BLOCK_SIZE || q + 4 + bs > n) break;
         if (out && o0 + k < cap) out[o0 + k] = q;
         if (rel && k < SC) {
             acc |= (q - cut) << (16 * (k & 3));

@@ -533,6 +533,188 @@ int FileReader::read_device(ChainContext &cc, ReadBatch &b, const std::string &p
     return 0;
 }
 
+// ----------------------------------------------------------------------------------- indexed reads
+bool FileReader::index_beside(const std::string &path, std::string &bai, std::string &why) {
+    struct stat sf, sb;
+    if (stat(path.c_str(), &sf) || !S_ISREG(sf.st_mode)) {
+        why = "the input is not a regular file";
+        return false;
+    }
+    std::vector<std::string> cand = {path + ".bai"};
+    if (path.size() > 4 && path.compare(path.size() - 4, 4, ".bam") == 0) cand.push_back(path.substr(0, path.size() - 4) + ".bai");
+    for (auto &c : cand) {
+        if (stat(c.c_str(), &sb) || !S_ISREG(sb.st_mode)) continue;
+        if (sb.st_mtim.tv_sec < sf.st_mtim.tv_sec || (sb.st_mtim.tv_sec == sf.st_mtim.tv_sec && sb.st_mtim.tv_nsec < sf.st_mtim.tv_nsec)) {
+            why = "the index " + c + " is older than the file";
+            return false;
+        }
+        bai = c;
+        return true;
+    }
+    why = "no index beside the file";
+    return false;
+}
+
+// BSIZE of the BGZF block whose 18-byte header is h (BC first in the extra field, as every writer here and
+// htslib places it); 0: no such header
+static uint64_t bgzf_block_size(const uint8_t *h) {
+    if (h[0] != 31 || h[1] != 139 || h[2] != 8 || h[3] != 4 || h[12] != 'B' || h[13] != 'C' || h[14] != 2 || h[15] != 0) return 0;
+    return (uint64_t)(h[16] | (h[17] << 8)) + 1;
+}
+
+// The header of a regular input file without reading the file: a BAM file's from its first whole BGZF blocks (a
+// 1 MiB prefix, growing by 8), a SAM file's from its leading '@' lines.  False: leave it to the reader.
+static bool peek_header(const std::string &path, BamFile &f) {
+    OwnedFd in(open(path.c_str(), O_RDONLY));
+    struct stat sf;
+    if (in.fd < 0 || fstat(in.fd, &sf) || !S_ISREG(sf.st_mode) || sf.st_size < 1) return false;
+    const uint64_t fsize = (uint64_t)sf.st_size;
+    std::string err;
+    for (uint64_t pre = std::min<uint64_t>(fsize, 1 << 20);; pre = std::min<uint64_t>(fsize, pre * 8)) {
+        bytevec head(pre), stream;
+        if (!pread_all(in.fd, head.data(), 0, pre, 1 << 20, 1)) return false;
+        f = BamFile();
+        if (head[0] == '@') {  // SAM: every header line is whole once a line that is not one has been seen
+            uint64_t p = 0;
+            while (p < pre && head[p] == '@') {
+                const void *nl = memchr(head.data() + p, '\n', pre - p);
+                if (!nl) break;
+                p = (uint64_t)((const uint8_t *)nl - head.data()) + 1;
+            }
+            if ((p < pre && head[p] != '@') || pre == fsize)
+                return sam_header_model(std::string((const char *)head.data(), p < pre && head[p] != '@' ? p : pre), f, err);
+        } else {
+            uint64_t whole = 0;
+            while (whole + 18 <= pre) {
+                const uint64_t bs = bgzf_block_size(head.data() + whole);
+                if (!bs || whole + bs > pre) break;
+                whole += bs;
+            }
+            size_t rec_base = 0;
+            if (whole && bgzf_inflate_all(head.data(), whole, stream, 1, err) && bam_parse_header(stream.data(), stream.size(), f, err, &rec_base))
+                return true;
+            if (pre == fsize) return false;
+        }
+    }
+}
+
+int FileReader::read_indexed(ChainContext &cc, ReadBatch &b, const std::string &path) {
+    const auto t0 = clk();
+    auto *flt = dynamic_cast<Filter *>(sink_);
+    std::string bai_path, why, err;
+    auto full_scan = [&](const std::string &reason) {
+        if (verbose_) fprintf(stderr, "[openge] FileReader: full scan, %s\n", reason.c_str());
+        return 1;
+    };
+    if (!flt || !index_beside(path, bai_path, why)) return full_scan(why);
+    const int threads = cc.threads > 0 ? cc.threads : 8;
+    bytevec bai;
+    if (!read_file_bytes(bai_path, bai, threads, err)) return full_scan("the index cannot be read: " + err);
+    OwnedFd in(open(path.c_str(), O_RDONLY));
+    struct stat sf;
+    if (in.fd < 0 || fstat(in.fd, &sf)) return full_scan("the file cannot be opened");
+    const uint64_t fsize = (uint64_t)sf.st_size;
+    // ---- the header, from the file's first blocks
+    BamFile f;
+    if (!peek_header(path, f)) return full_scan("the header cannot be read from the first blocks");
+    const int32_t n_ref = (int32_t)f.ref_names.size();
+    std::vector<oge_region> regions;
+    if (flt->parseRegions(f.header, regions)) return -1;
+    // ---- index -> ranges -> spans of the file
+    oge_bai *ix = nullptr;
+    if (oge_bai_open(cc.ctx, bai.data(), bai.size(), n_ref, &ix)) return full_scan(oge_last_error(cc.ctx));
+    struct CloseBai {
+        oge_bai *p;
+        ~CloseBai() { oge_bai_close(p); }
+    } close_bai{ix};
+    const uint64_t *d_ranges = nullptr;
+    uint64_t n_ranges = 0;
+    if (oge_bai_query_dev(cc.ctx, ix, regions.data(), regions.size(), kIndexWiden, &d_ranges, &n_ranges)) return full_scan(oge_last_error(cc.ctx));
+    std::vector<uint64_t> ranges(2 * n_ranges), span_file, span_z = {0};
+    if (n_ranges && oge_memcpy(cc.ctx, ranges.data(), d_ranges, n_ranges * 16, 2)) return full_scan(oge_last_error(cc.ctx));
+    uint64_t span_end = 0;
+    for (uint64_t r = 0; r < n_ranges; ++r) {
+        const uint64_t beg = ranges[2 * r], end = ranges[2 * r + 1];
+        const uint64_t sb = beg >> 16;
+        uint64_t se = end >> 16;
+        if (beg >= end || se > fsize) return full_scan("a range of the index is empty or points past the file");
+        if (end & 0xFFFF) {  // the block that holds end - 1: its size from its header
+            uint8_t h[18];
+            if (se + 18 > fsize || !pread_all(in.fd, h, se, 18, 18, 1) || !bgzf_block_size(h) || se + bgzf_block_size(h) > fsize)
+                return full_scan("a range of the index does not end in a BGZF block");
+            se += bgzf_block_size(h);
+        }
+        if (sb >= se) return full_scan("a range of the index is empty or points past the file");
+        if (!span_file.empty() && sb <= span_end + 65536) {  // touching or less than one maximal block apart
+            if (sb < span_file.back()) return full_scan("the ranges of the index do not ascend");
+            span_end = std::max(span_end, se);
+        } else {
+            if (!span_file.empty()) span_z.push_back(span_z.back() + (span_end - span_file.back()));
+            span_file.push_back(sb);
+            span_end = se;
+        }
+    }
+    if (!span_file.empty()) span_z.push_back(span_z.back() + (span_end - span_file.back()));
+    const uint64_t zbytes = span_z.back();
+    // a list that names most of the file: the full scan streams it with less work than spans and a pack
+    if (zbytes > fsize / 2) return full_scan("the index names more than half of the file");
+    const auto t1 = clk();
+    DevBuf dz(cc.ctx), dout(cc.ctx), doff(cc.ctx);
+    uint64_t n = 0, bytes = 0, blocks = 0;
+    if (n_ranges) {
+        // the compressed spans, their inflated form and the packed records are in HBM together
+        uint64_t fr = 0, tot = 0;
+        if (oge_mem_info(cc.ctx, &fr, &tot) || zbytes / 10 * 60 > fr) return full_scan("the spans of the index do not fit beside their records");
+        if (dz.alloc(zbytes + 16)) return full_scan(oge_last_error(cc.ctx));
+        // long spans stream through page-locked buffers; runs of short ones go up together from one host buffer
+        constexpr uint64_t kLong = 8ull << 20;
+        bytevec stage;
+        for (size_t s = 0; s < span_file.size();) {
+            const uint64_t len = span_z[s + 1] - span_z[s];
+            if (len >= kLong) {
+                if (range_to_device(cc.ctx, in.fd, span_file[s], len, dz.as<uint8_t>() + span_z[s], std::min<uint64_t>(len, 64ull << 20), 4 << 20))
+                    return full_scan("the file cannot be read");
+                ++s;
+                continue;
+            }
+            size_t e = s;
+            while (e < span_file.size() && span_z[e + 1] - span_z[e] < kLong && span_z[e + 1] - span_z[s] <= (256ull << 20)) ++e;
+            stage.resize(span_z[e] - span_z[s]);
+            for (size_t k = s; k < e; ++k)
+                if (!pread_all(in.fd, stage.data() + (span_z[k] - span_z[s]), span_file[k], span_z[k + 1] - span_z[k], 4 << 20, threads))
+                    return full_scan("the file cannot be read");
+            if (oge_memcpy(cc.ctx, dz.as<uint8_t>() + span_z[s], stage.data(), stage.size(), 1)) return full_scan(oge_last_error(cc.ctx));
+            s = e;
+        }
+        uint8_t *d_recs = nullptr;
+        uint64_t *d_off = nullptr;
+        if (oge_bam_decode_ranges_dev(cc.ctx, dz.as<uint8_t>(), zbytes, span_z.data(), span_file.data(), span_file.size(), d_ranges, n_ranges,
+                                      n_ref, &d_recs, &d_off, &n, &bytes))
+            return full_scan(oge_last_error(cc.ctx));
+        dout.adopt(d_recs, bytes + 64);
+        doff.adopt(d_off, (n + 1) * 8);
+        oge_ctx_counter(cc.ctx, "baiq_blocks", &blocks);
+    }
+    if (!n) {  // no record: an empty batch of its own
+        const uint64_t zero = 0;
+        if (dout.alloc(64) || doff.alloc(8) || oge_memcpy(cc.ctx, doff.as<void>(), &zero, 8, 1)) return full_scan(oge_last_error(cc.ctx));
+        bytes = 0;
+    }
+    b.header = f.header;
+    b.ref_names = f.ref_names;
+    b.n = n;
+    b.d_recs = (uint8_t *)dout.release();
+    b.d_offs = (uint64_t *)doff.release();
+    b.d_bytes = bytes;
+    b.dev_valid = true;
+    b.host_valid = false;
+    if (verbose_)
+        fprintf(stderr, "[openge] FileReader (indexed): %zu regions, %llu ranges, %llu blocks, %llu of %llu bytes read (index and spans %.3f s, "
+                        "load and decode %.3f s)\n", regions.size(), (unsigned long long)n_ranges, (unsigned long long)blocks,
+                (unsigned long long)zbytes, (unsigned long long)fsize, sec(t0, t1), sec(t1, clk()));
+    return 0;
+}
+
 // True when the next module takes per-rank input shards (run_ranks: the coordinate ReadSorter, or a
 // standalone MarkDuplicates).
 bool FileReader::sink_takes_shards() const {
@@ -621,6 +803,14 @@ int FileReader::read_sharded(ChainContext &cc, ReadBatch &b, const std::string &
 
 int FileReader::runInternal(ChainContext &cc, ReadBatch &b) {
     if (files_.empty()) files_.push_back("stdin");
+    // regions are parsed against the first input's dictionary: from a look at its header, so that a region or a
+    // line of the list that does not parse ends the chain before any input is read (a pipe cannot be looked at:
+    // there the Filter reports it, after the read and before anything is written)
+    if (auto *flt = dynamic_cast<Filter *>(sink_); flt && flt->hasRegions() && files_[0] != "stdin" && files_[0] != "-") {
+        BamFile hf;
+        std::vector<oge_region> parsed;
+        if (peek_header(files_[0], hf) && flt->parseRegions(hf.header, parsed)) return -1;
+    }
     std::vector<uint64_t> file_end;  // record count after each file
     const char *rd = getenv("OGE_READER");
     // one SAM file (first byte '@'): its text into HBM and parsed there; with --gpus on rank 0, then run_ranks'
@@ -639,6 +829,11 @@ int FileReader::runInternal(ChainContext &cc, ReadBatch &b) {
         if (r <= 0) return r;  // 1: the host reader reports why the file cannot be read
     }
     if (files_.size() == 1 && files_[0] != "stdin" && files_[0] != "-" && !one_sam && !(rd && std::string(rd) == "host")) {
+        auto *flt = dynamic_cast<Filter *>(sink_);
+        if (flt && flt->hasRegions() && cc.gpus == 1 && !no_index_) {
+            const int ri = read_indexed(cc, b, files_[0]);
+            if (ri <= 0) return ri;  // 1: the full scan below
+        }
         const int r = read_device(cc, b, files_[0]);
         if (r <= 0) return r;  // 1: fall through to the host reader (it reports format errors)
     }
@@ -830,32 +1025,82 @@ bool Filter::setReadLengths(const std::string &s) {
     return true;
 }
 
-int Filter::runInternal(ChainContext &cc, ReadBatch &b) {
-    oge_filter_opts o = opts_;
-    if (has_region_) {
-        if (verbose_) fprintf(stderr, "Filtering to region %s\n", region_.c_str());
-        std::string names;
-        std::vector<int64_t> lens;
-        for (auto &sq : b.header.sq) {
-            names += sq.name;
-            names.push_back('\0');
-            lens.push_back(sq.length);
+bool Filter::setRegionsFile(const std::string &path) {
+    FILE *f = fopen(path.c_str(), "r");
+    if (!f) {
+        fprintf(stderr, "openge: cannot read the regions file %s\n", path.c_str());
+        return false;
+    }
+    regions_file_ = path;
+    std::string line;
+    uint64_t no = 0;
+    for (int c = 0; c != EOF;) {
+        c = fgetc(f);
+        if (c != '\n' && c != EOF) {
+            line.push_back((char)c);
+            continue;
         }
-        if (oge_parse_region(region_.c_str(), names.data(), (int32_t)lens.size(), lens.data(), &o)) {
+        if (c == EOF && line.empty()) break;
+        ++no;
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (!line.empty() && line[0] != '#') more_regions_.push_back({line, no});
+        line.clear();
+    }
+    fclose(f);
+    return true;
+}
+
+int Filter::parseRegions(const BamHeaderModel &h, std::vector<oge_region> &out) const {
+    std::string names;
+    std::vector<int64_t> lens;
+    for (auto &sq : h.sq) {
+        names += sq.name;
+        names.push_back('\0');
+        lens.push_back(sq.length);
+    }
+    auto one = [&](const std::string &text, uint64_t line) {
+        oge_filter_opts o = opts_;
+        if (oge_parse_region(text.c_str(), names.data(), (int32_t)lens.size(), lens.data(), &o)) {
             // filter.cpp:243-247: the parse error, then the generic message, then exit(-1)
             const std::string why = oge_last_error(nullptr);
-            if (why.rfind("ERROR: could not parse", 0) != 0) fprintf(stderr, "%s\n", why.c_str());
+            if (line) fprintf(stderr, "openge: %s line %llu: %s\n", regions_file_.c_str(), (unsigned long long)line, why.c_str());
+            else if (why.rfind("ERROR: could not parse", 0) != 0) fprintf(stderr, "%s\n", why.c_str());
             fprintf(stderr, "ERROR: could not parse region'%s'\n"
                             "Check that region description is in valid format (see documentation) and that the "
-                            "coordinates are valid\n", region_.c_str());
-            return -1;
+                            "coordinates are valid\n", text.c_str());
+            return false;
+        }
+        out.push_back({o.ref_id, o.left_pos, o.right_pos});
+        return true;
+    };
+    if (has_region_ && !one(region_, 0)) return -1;
+    for (auto &rl : more_regions_)
+        if (!one(rl.text, rl.line)) return -1;
+    return 0;
+}
+
+int Filter::runInternal(ChainContext &cc, ReadBatch &b) {
+    oge_filter_opts o = opts_;
+    std::vector<oge_region> regions;
+    if (hasRegions()) {
+        if (verbose_ && has_region_) fprintf(stderr, "Filtering to region %s\n", region_.c_str());
+        if (parseRegions(b.header, regions)) return -1;
+        if (verbose_ && !more_regions_.empty()) fprintf(stderr, "Filtering to %zu regions\n", regions.size());
+        if (regions.size() == 1) {  // one region in all: the single-region predicate
+            o.has_region = 1;
+            o.ref_id = regions[0].ref_id;
+            o.left_pos = regions[0].left_pos;
+            o.right_pos = regions[0].right_pos;
+            regions.clear();
         }
     }
     if (cc.to_device(b)) return -1;
     DevBuf out(cc.ctx), out_off(cc.ctx);
     if (out.alloc(b.d_bytes + 64) || out_off.alloc((b.n + 1) * 8)) return cc.fail("device allocation");
     uint64_t m = 0, bytes = 0;
-    int rc = oge_filter_records_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &o, out.as<uint8_t>(), out_off.as<uint64_t>(), &m);
+    int rc = regions.empty() ? oge_filter_records_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &o, out.as<uint8_t>(), out_off.as<uint64_t>(), &m)
+                             : oge_filter_regions_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &o, regions.data(), regions.size(),
+                                                      out.as<uint8_t>(), out_off.as<uint64_t>(), &m);
     if (!rc) rc = oge_memcpy(cc.ctx, &bytes, out_off.as<uint64_t>() + m, 8, 2);
     if (!rc) rc = oge_ctx_sync(cc.ctx);
     if (rc) return cc.fail("Filter");

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/openge_hip.h"
+#include "bam_layout.h"
 #include "bamio.h"
 #include "file_load.h"
 
@@ -106,12 +107,25 @@ protected:
 // the reference's MultiReader does (a ByPosition merge of the file heads,
 // util/read_stream_reader.h:132-153) unless a ReadSorter follows, which makes the interleaving
 // irrelevant; the header is the first file's (a differing dictionary only warns, :116-124).
+// The index is asked for [left_pos - kIndexWiden, right_pos]: the Filter keeps a record when pos + l_seq >=
+// left_pos, and l_seq is below the record walk's block_size cap (OGE_MAX_BLOCK_SIZE, the constant inflate.hip's
+// walk tests), the largest record the device reader admits; the index itself was built from reference spans,
+// which can be shorter (soft clips, insertions).  A record beyond the cap inside the decoded ranges fails the
+// walk and gives the full scan; one outside them that reaches a region with more than the cap of clipped or
+// inserted bases is not found through the index (the host reader, which the full scan of such a file falls to,
+// keeps it).
+constexpr int32_t kIndexWiden = OGE_MAX_BLOCK_SIZE;
+
 class FileReader : public AlgorithmModule {
 public:
     FileReader() : AlgorithmModule("FileReader") {}
     void addFile(const std::string &f) { files_.push_back(f); }
     void addFiles(const std::vector<std::string> &f) { files_.insert(files_.end(), f.begin(), f.end()); }
     void setLoadStringData(bool) {}  // the record arena always keeps the full record bytes
+    void setNoIndex(bool on) { no_index_ = on; }  // --noindex: never read a .bai
+    // <path>.bai, or <path minus ".bam">.bai, when it exists and is not older than the file; else `why` says
+    // what is missing
+    static bool index_beside(const std::string &path, std::string &bai, std::string &why);
     // outside a chain (compare_files): this reader's files into b, the records resident in HBM
     int load(ChainContext &cc, ReadBatch &b) {
         const int rc = runInternal(cc, b);
@@ -124,6 +138,13 @@ protected:
     int read_device(ChainContext &cc, ReadBatch &b, const std::string &path);
     // --gpus G: every rank reads and decodes its own byte range of the one input file (b.shards)
     int read_sharded(ChainContext &cc, ReadBatch &b, const std::string &path);
+    // FileReader -> Filter with regions, one BAM file, one GPU, an index beside the file: only the blocks the
+    // index names for the regions (widened by kIndexWiden) are read, inflated and walked (oge_bai_open,
+    // oge_bai_query_dev, oge_bam_decode_ranges_dev); the Filter then runs over those records as over all of
+    // them.  0 = done, 1 = the full scan takes over (one [openge] line under -v says why), -1 = a region does
+    // not parse (reported).
+    int read_indexed(ChainContext &cc, ReadBatch &b, const std::string &path);
+    bool no_index_ = false;
     bool sink_takes_shards() const;
     bool sink_sorts() const;
     static int merge_inputs(ReadBatch &b, const std::vector<uint64_t> &file_end, int threads);
@@ -134,11 +155,22 @@ protected:
 // device compaction (oge_filter_records_dev).  Trimming (setTrimBeginLength/EndLength, `view -B/-E`)
 // drops the reads it would leave empty (len > trim total); the cut itself is made where the FASTQ text
 // is formatted (FileWriter::setTrim), the only format the reference allows it with.
+// addRegion / setRegionsFile (view / mergesort -L): any number of regions in setRegion's syntax; a record passes
+// when at least one of them holds, and is written once (oge_filter_regions_dev when there is more than one).
 class Filter : public AlgorithmModule {
 public:
     Filter() : AlgorithmModule("Filter") { oge_filter_opts_init(&opts_); }
     void setRegion(const std::string &region) { region_ = region; has_region_ = true; }
     std::string getRegion() const { return region_; }
+    void addRegion(const std::string &region) { more_regions_.push_back({region, 0}); }
+    // one region per line, blank lines and lines starting with '#' skipped; false (with a message) when the
+    // file cannot be read.  The lines are parsed against the header's dictionary: by the FileReader from a look
+    // at the first input's header, so a line that does not parse ends the chain with its line number before any
+    // input is read, and again when the module runs (a pipe's header is known only then).
+    bool setRegionsFile(const std::string &path);
+    bool hasRegions() const { return has_region_ || !more_regions_.empty(); }
+    // every region (-r first, then the list) against the header's dictionary; -1 with the messages printed
+    int parseRegions(const BamHeaderModel &h, std::vector<oge_region> &out) const;
     void setCountLimit(int ct) { opts_.count_limit = ct < 0 ? 0 : (uint64_t)ct; }
     size_t getCountLimit() const { return opts_.count_limit; }
     void setQualityLimit(int mapq) { opts_.mapq_min = mapq; }
@@ -153,6 +185,12 @@ protected:
     int runInternal(ChainContext &cc, ReadBatch &b) override;
     std::string region_;
     bool has_region_ = false;
+    struct RegionLine {
+        std::string text;
+        uint64_t line;  // 1-based line of the -L file, 0: from addRegion
+    };
+    std::vector<RegionLine> more_regions_;
+    std::string regions_file_;
     int trim_begin_ = 0, trim_end_ = 0;
     oge_filter_opts opts_;
 };

@@ -4,6 +4,11 @@
 // same module chain the reference builds (commands/command_mergesort.cpp:68-117,
 // command_dedup.cpp:48-69, command_localrealign.cpp:37-75) out of the modules in modules.h.
 // `view` is FileReader -> Filter -> FileWriter (commands/command_view.cpp:44-100), SAM to stdout by default.
+// -L FILE (view, mergesort, sort; not in the reference): a list of regions in the syntax of -r, one per line; a read
+// is kept when it passes -r's test for at least one of them (and for -r's own region, when both are given).
+// With regions and an index beside the one BAM input (in.bam.bai or in.bai, not older than the file) the reader takes only
+// the blocks the index names (FileReader::read_indexed) and the input is not prefetched; anything
+// wrong with the index gives the full scan, with one [openge] line under -v; --noindex never looks for an index.
 // `index`, `stats`, `count` and `coverage` are one whole-file device call each (index_bam_file,
 // stats_bam_file, count_bam_file, coverage_bam_file in modules.cpp; commands/command_stats.cpp,
 // command_count.cpp, command_coverage.cpp for the last three).
@@ -61,10 +66,12 @@ const Opt kGlobal[] = {{"v", "verbose", false}, {"t", "threads", true}, {"d", "n
                        {"", "deflate-search", true}};
 const Opt kMergesort[] = {{"o", "out", true}, {"r", "region", true},  {"q", "mapq", true},
                           {"b", "byname", false}, {"n", "n", true}, {"C", "compresstempfiles", false},
-                          {"M", "markduplicates", false}, {"R", "removeduplicates", false}, {"", "index", false}};
+                          {"M", "markduplicates", false}, {"R", "removeduplicates", false}, {"", "index", false},
+                          {"L", "regions", true}, {"", "noindex", false}};
 const Opt kDedup[] = {{"o", "out", true}, {"r", "remove", false}, {"", "index", false}};
 const Opt kView[] = {{"o", "out", true}, {"n", "count", true}, {"q", "mapq", true}, {"l", "length", true},
-                     {"B", "trimbegin", true}, {"E", "trimend", true}, {"r", "region", true}};
+                     {"B", "trimbegin", true}, {"E", "trimend", true}, {"r", "region", true}, {"L", "regions", true},
+                     {"", "noindex", false}};
 const Opt kIndex[] = {{"o", "out", true}};
 const Opt kStats[] = {{"I", "inserts", false}, {"L", "lengths", false}};
 const Opt kCoverage[] = {{"o", "out", true}, {"b", "binsize", true}, {"", "omituncoveredbases", false},
@@ -133,10 +140,16 @@ void usage_top() {
                     "          compare, version\n"
                     "\n    Inputs are BAM files or SAM text (first byte '@'; also on stdin, and mixed with BAM files); SAM is parsed\n"
                     "    on the GPU.  index takes BAM only.\n"
-                    "\n    openge view [-o out] [-n N] [-q MAPQ] [-l LEN] [-r REGION] [-B N] [-E N] in.bam|in.sam\n"
+                    "\n    openge view [-o out] [-n N] [-q MAPQ] [-l LEN] [-r REGION] [-L FILE] [-B N] [-E N] in.bam|in.sam\n"
                     "                                        the reads that pass the filters (-l: 64, 64-72, -64 or +64), as SAM\n"
                     "                                        on stdout, else in the format of -F or of the output name's suffix;\n"
                     "                                        -B / -E trim bases from the read ends, FASTQ only\n"
+                    "    view / mergesort / sort -L FILE     keep the reads of at least one region of FILE (one per line in the\n"
+                    "                                        syntax of -r; blank lines and lines starting with # are skipped),\n"
+                    "                                        each read once, in input order; with -r: of either\n"
+                    "    view / mergesort / sort -r / -L     with in.bam.bai (or in.bai) beside one BAM input, not older than it,\n"
+                    "                                        only the blocks the index names are read; --noindex: always the\n"
+                    "                                        whole file.  The output is the same either way.\n"
                     "    -F sam | fastq | bam                output format of view, mergesort, sort and dedup (SAM and FASTQ text are\n"
                     "                                        formatted on the GPU; FASTQ only from view to stdout; not with --gpus\n"
                     "                                        or --index)\n"
@@ -311,10 +324,23 @@ int main(int argc, const char **argv) {
             return -1;
         }
     }
+    if (p.count("regions")) {  // an unreadable -L file is refused before anything is read
+        const std::string rf = p.get("regions", "");
+        FILE *f = fopen(rf.c_str(), "r");
+        if (!f) {
+            fprintf(stderr, "openge: cannot read the regions file %s\n", rf.c_str());
+            return -1;
+        }
+        fclose(f);
+    }
     timeval t0;
     gettimeofday(&t0, nullptr);
-    // one input file on one GPU: its bytes come off the disk / page cache while HIP initialises
-    if (p.inputs.size() == 1 && p.inputs[0] != "stdin" && cc.gpus == 1) prefetch_input(p.inputs[0]);
+    // one input file on one GPU: its bytes come off the disk / page cache while HIP initialises -- unless the
+    // reader will take only the blocks an index names (regions, an index beside the file, no --noindex)
+    std::string bai_path, bai_why;
+    const bool indexed = (cmd == "view" || cmd == "mergesort") && (p.count("region") || p.count("regions")) && !p.count("noindex") &&
+                         p.inputs.size() == 1 && cc.gpus == 1 && FileReader::index_beside(p.inputs[0], bai_path, bai_why);
+    if (p.inputs.size() == 1 && p.inputs[0] != "stdin" && cc.gpus == 1 && !indexed) prefetch_input(p.inputs[0]);
     if (oge_ctx_create(cc.device, &cc.ctx)) {
         fprintf(stderr, "openge: %s\n", oge_last_error(nullptr));
         return -1;
@@ -346,6 +372,7 @@ int main(int argc, const char **argv) {
     FileReader reader;
     FileWriter writer;
     reader.addFiles(p.inputs);
+    reader.setNoIndex(p.count("noindex"));
     writer.setFilename(p.get("out", "stdout"));
     writer.setIndex(p.count("index"));
     if (!p.count("nopg")) writer.addProgramLine(command_line);
@@ -361,6 +388,7 @@ int main(int argc, const char **argv) {
         if (p.count("trimbegin")) filter.setTrimBeginLength(atoi(p.get("trimbegin", "0").c_str()));
         if (p.count("trimend")) filter.setTrimEndLength(atoi(p.get("trimend", "0").c_str()));
         if (p.count("region")) filter.setRegion(p.get("region", ""));
+        if (p.count("regions") && !filter.setRegionsFile(p.get("regions", ""))) return -1;
         writer.setTrim(atoi(p.get("trimbegin", "0").c_str()), atoi(p.get("trimend", "0").c_str()));
         writer.setDefaultFormat(out_stdout ? FORMAT_SAM : FORMAT_BAM);
         reader.addSink(&filter);
@@ -374,8 +402,9 @@ int main(int argc, const char **argv) {
         sorter.setSortBy(p.count("byname") ? BamHeaderModel::QUERYNAME : BamHeaderModel::COORDINATE);
         sorter.setCompressTempFiles(p.count("compresstempfiles"));
         sorter.setAlignmentsPerTempfile(atoi(p.get("n", "500000").c_str()));
-        if (p.count("region") || p.count("mapq")) {  // command_mergesort.cpp:82-92
+        if (p.count("region") || p.count("mapq") || p.count("regions")) {  // command_mergesort.cpp:82-92
             if (p.count("region")) filter.setRegion(p.get("region", ""));
+            if (p.count("regions") && !filter.setRegionsFile(p.get("regions", ""))) return -1;
             if (p.count("mapq")) filter.setQualityLimit(atoi(p.get("mapq", "0").c_str()));
             reader.addSink(&filter);
             filter.addSink(&sorter);

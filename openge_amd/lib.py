@@ -50,6 +50,12 @@ class FilterOpts(C.Structure):
                                          "max_len", "trim_total")] + [("count_limit", C.c_uint64)]
 
 
+class Region(C.Structure):
+    """oge_region: one region of a region list, the ref_id / left_pos / right_pos of oge_filter_opts."""
+
+    _fields_ = [(k, C.c_int32) for k in ("ref_id", "left_pos", "right_pos")]
+
+
 class BamStats(C.Structure):
     """Mirror of oge_bam_stats (include/openge_hip.h)."""
 
@@ -328,6 +334,13 @@ def lib() -> C.CDLL:
         "oge_filter_opts_init": (None, [vp]),
         "oge_parse_region": (C.c_int, [C.c_char_p, C.c_char_p, i32, vp, vp]),
         "oge_filter_records_dev": (C.c_int, [vp, vp, vp, u64, vp, vp, vp, C.POINTER(u64)]),
+        "oge_bai_open": (C.c_int, [vp, vp, u64, i32, C.POINTER(vp)]),
+        "oge_bai_close": (None, [vp]),
+        "oge_bai_query_dev": (C.c_int, [vp, vp, vp, u64, i32, C.POINTER(vp), C.POINTER(u64)]),
+        "oge_bai_query": (C.c_int, [vp, vp, vp, u64, i32, vp, u64, C.POINTER(u64)]),
+        "oge_bam_decode_ranges_dev": (C.c_int, [vp, vp, u64, vp, vp, u64, vp, u64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64),
+                                                C.POINTER(u64)]),
+        "oge_filter_regions_dev": (C.c_int, [vp, vp, vp, u64, vp, vp, u64, vp, vp, C.POINTER(u64)]),
         "oge_sort_name_dev": (C.c_int, [vp, vp, vp, u64, vp]),
         "oge_sort_name": (C.c_int, [vp, vp, u64, vp, u64, vp]),
         "oge_bgzf_index_dev": (C.c_int, [vp, vp, u64, vp, vp, vp, vp, u64, C.POINTER(u64)]),
@@ -962,6 +975,58 @@ class Context:
         m = C.c_uint64()
         check(lib().oge_filter_records_dev(self.h, d_recs, d_off, n, C.byref(opts), d_out, d_out_off, C.byref(m)),
               self.h)
+        return m.value
+
+    def bai_open(self, bai: bytes, n_ref_expected: int = -1) -> int:
+        """oge_bai_open -> the handle (release it with bai_close)."""
+        h = C.c_void_p()
+        check(lib().oge_bai_open(self.h, bai, len(bai), n_ref_expected, C.byref(h)), self.h)
+        return h.value
+
+    def bai_close(self, handle: int) -> None:
+        lib().oge_bai_close(handle)
+
+    def bai_query(self, handle: int, regions, widen: int = 0, cap: int | None = None) -> list[tuple[int, int]]:
+        """oge_bai_query: the merged (beg, end) virtual-offset ranges of (ref_id, left_pos, right_pos) triples."""
+        arr = (Region * max(len(regions), 1))(*[Region(*r) for r in regions])
+        n = C.c_uint64()
+        if cap is None:  # sized by the device form's count
+            d = C.c_void_p()
+            check(lib().oge_bai_query_dev(self.h, handle, arr, len(regions), widen, C.byref(d), C.byref(n)), self.h)
+            cap = n.value
+        out = np.zeros(2 * max(cap, 1), dtype=np.uint64)
+        check(lib().oge_bai_query(self.h, handle, arr, len(regions), widen, _ptr(out), cap, C.byref(n)), self.h)
+        return [(int(out[2 * k]), int(out[2 * k + 1])) for k in range(n.value)]
+
+    def bai_query_dev(self, handle: int, regions, widen: int = 0) -> tuple[int, int]:
+        """oge_bai_query_dev -> (device pointer of the pairs or 0, n_ranges)."""
+        arr = (Region * max(len(regions), 1))(*[Region(*r) for r in regions])
+        d, n = C.c_void_p(), C.c_uint64()
+        check(lib().oge_bai_query_dev(self.h, handle, arr, len(regions), widen, C.byref(d), C.byref(n)), self.h)
+        return d.value or 0, n.value
+
+    def bam_decode_ranges_dev(self, d_z: int, zbytes: int, span_z, span_file, d_ranges: int, n_ranges: int, n_ref: int) -> tuple[bytes, list[int]]:
+        """oge_bam_decode_ranges_dev -> (the packed records, their n + 1 offsets), copied to the host."""
+        sz, sf = np.asarray(span_z, dtype=np.uint64), np.asarray(span_file, dtype=np.uint64)
+        dr, do, n, nb = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        check(lib().oge_bam_decode_ranges_dev(self.h, d_z, zbytes, _ptr(sz), _ptr(sf), len(sf), d_ranges, n_ranges, n_ref, C.byref(dr),
+                                              C.byref(do), C.byref(n), C.byref(nb)), self.h)
+        try:
+            if not n.value:
+                return b"", [0]
+            offs = np.frombuffer(self._fetch(do.value, 8 * (n.value + 1)), dtype=np.uint64)
+            return self._fetch(dr.value, nb.value), [int(x) for x in offs]
+        finally:  # the arena and the offsets are the caller's
+            for p in (dr.value, do.value):
+                if p:
+                    lib().oge_dev_free(self.h, p)
+
+    def filter_regions_dev(self, d_recs, d_off, n: int, opts: "FilterOpts", regions, d_out, d_out_off) -> int:
+        """oge_filter_regions_dev; regions: (ref_id, left_pos, right_pos) triples (a host list)."""
+        arr = (Region * max(len(regions), 1))(*[Region(*r) for r in regions])
+        m = C.c_uint64()
+        check(lib().oge_filter_regions_dev(self.h, d_recs, d_off, n, C.byref(opts), arr if regions else None, len(regions),
+                                           d_out, d_out_off, C.byref(m)), self.h)
         return m.value
 
     def sort_name(self, recs: np.ndarray, offs: np.ndarray, n: int) -> np.ndarray:
