@@ -77,6 +77,22 @@ def digest(recs: np.ndarray, offs) -> dict:
     return {"stream_sha256": h.hexdigest(), "per_record": np.array(per, dtype=np.uint64)}
 
 
+def realign_both(ctx, monkeypatch, h, recs, offs, fa, iv):
+    """oge_localrealign with phase B on the host threads, then on the device: the same records, scan pairs,
+    compare counts and realigned reads -> (output stream, offsets, host-run stats, device-run stats)."""
+    monkeypatch.setenv("OGE_REALIGN_DEVICE_PREP", "0")
+    out0, oo0, st0 = ctx.localrealign(h, recs, offs, len(offs) - 1, fa, iv)
+    monkeypatch.setenv("OGE_REALIGN_DEVICE_PREP", "1")
+    out1, oo1, st1 = ctx.localrealign(h, recs, offs, len(offs) - 1, fa, iv)
+    monkeypatch.delenv("OGE_REALIGN_DEVICE_PREP")
+    assert st0["device_prep"] == 0 and st1["device_prep"] == 1
+    b0, b1 = bytes(out0[:int(oo0[-1])]), bytes(out1[:int(oo1[-1])])
+    assert b0 == b1 and list(oo0) == list(oo1)
+    for k in ("scan_pairs", "scan_ops", "intervals_cleaned", "reads_realigned"):
+        assert st0[k] == st1[k], k
+    return out1, oo1, st0, st1
+
+
 def first_difference(a_recs, a_offs, b_recs, b_offs) -> str:
     """Human-readable description of the first differing record (for assertion messages)."""
     n = min(len(a_offs), len(b_offs))

@@ -39,6 +39,20 @@ def test_gpu_scan_bitplane_path(ctx, seed):
     assert np.array_equal(gi, oi)
 
 
+@pytest.mark.parametrize("seed", range(2))
+def test_gpu_scan_bitplane_path_iupac(ctx, seed):
+    """The device-built batch decodes SEQ through "=ACMGRSVTWYHKDBN": the bit-plane kernels meet '=' and the
+    IUPAC letters, which are upper case (no switch to the byte-wise kernel) and never regular (no mismatch
+    weight on either side).  Same sizes as test_gpu_scan_bitplane_path."""
+    rng = np.random.default_rng(520 + seed)
+    b = random_batch(rng, n_cons=16, reads_per=10, cons_len=(30, 700), read_len=(5, 300), alphabet=b"ACGTNRYKMSW=",
+                     qual_max=(120 if seed % 2 else 93))
+    gi, gs = ctx.realign_scan(*b)
+    oi, os_ = oracle.realign_scan(*b)
+    assert np.array_equal(gs, os_)
+    assert np.array_equal(gi, oi)
+
+
 def test_gpu_scan_realistic_sizes(ctx):
     rng = np.random.default_rng(7)
     b = random_batch(rng, n_cons=64, reads_per=24, cons_len=(250, 600), read_len=(100, 151), alphabet=b"ACGT",
@@ -95,17 +109,8 @@ def test_gpu_contig_sharded_realign_equals_reference(ctx, tmp_path, world):
 
 
 def _realign_both(ctx, monkeypatch, h, recs, offs, fa, iv):
-    monkeypatch.setenv("OGE_REALIGN_DEVICE_PREP", "0")
-    out0, oo0, st0 = ctx.localrealign(h, recs, offs, len(offs) - 1, fa, iv)
-    monkeypatch.setenv("OGE_REALIGN_DEVICE_PREP", "1")
-    out1, oo1, st1 = ctx.localrealign(h, recs, offs, len(offs) - 1, fa, iv)
-    monkeypatch.delenv("OGE_REALIGN_DEVICE_PREP")
-    assert st0["device_prep"] == 0 and st1["device_prep"] == 1
-    b0, b1 = bytes(out0[:int(oo0[-1])]), bytes(out1[:int(oo1[-1])])
-    assert b0 == b1 and list(oo0) == list(oo1)
-    for k in ("scan_pairs", "scan_ops", "intervals_cleaned", "reads_realigned"):
-        assert st0[k] == st1[k], k
-    return st1
+    import realign_util as R
+    return R.realign_both(ctx, monkeypatch, h, recs, offs, fa, iv)[3]
 
 
 @pytest.mark.parametrize("name", RL_CASES)
