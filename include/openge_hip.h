@@ -406,6 +406,11 @@ uint64_t oge_bgzf_bound(uint64_t n);
  * OGE_DEFL_NEAR, OGE_DEFL_SPAN or both; level 0 and the stored-block fallback ignore it. */
 int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t n, int level, uint8_t *d_dst,
                          uint64_t dst_cap, uint64_t *out_bytes);
+/* The block writer has two instances: blocks of at most this many bytes (header and footer included) are
+ * assembled three workgroups to a CU, larger ones two.  OGE_DEFL_EMIT_CAP (bytes, read per call) lowers
+ * the limit, 0 sends every block to the large instance; the bytes written are the same either way.  The
+ * counters "defl_emit_small" / "defl_emit_big" (oge_ctx_counter) give a call's blocks per instance. */
+uint32_t oge_defl_emit_cap(void);
 /* Host-buffer form (uploads, compresses, downloads); dst_cap >= the compressed size. */
 int oge_bgzf_deflate(oge_ctx *ctx, const uint8_t *src, uint64_t n, int level, uint8_t *dst, uint64_t dst_cap,
                      uint64_t *out_bytes);

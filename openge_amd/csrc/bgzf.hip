@@ -22,7 +22,8 @@
 //   k_scan_chunk / k_defl_advance   the blocks' offsets in the output stream.
 //   k_defl_emit    one 512-thread workgroup per payload: segment bit counts, block scan, bits written
 //                  into an LDS image of the whole BGZF block, CRC-32, then the block out at its final
-//                  offset with coalesced stores.
+//                  offset with coalesced stores.  Two instances by the block's size: a 46 KiB image, three
+//                  workgroups per CU, and the full 64 KiB image, two per CU.
 // Deterministic: the same input gives the same bytes (the candidate rounds fix what each position sees).
 #include <hip/hip_runtime.h>
 
@@ -1230,7 +1231,7 @@ __global__ void __launch_bounds__(64) k_defl_huff(const uint32_t *__restrict__ f
 }
 
 // ------------------------------------------------------------------------------------ emit
-// One 512-thread workgroup per payload (two per CU: 74 KiB of LDS).  The whole BGZF block is assembled in
+// One 512-thread workgroup per payload (two or three per CU, see k_defl_emit below).  The whole BGZF block is assembled in
 // LDS -- header, deflate bits, footer -- and written once, with coalesced dword stores, straight to its
 // final place in the output stream (offset = the chunk's base + the scan of the block sizes k_defl_huff
 // computed): no 64 KiB slot per block and no compaction copy (r02: each lane stored 4-byte words into its
@@ -1410,36 +1411,74 @@ __device__ __forceinline__ void seg_emit(const uint32_t (&w)[16], uint64_t lm, u
     bw.finish();
 }
 
-__global__ void __launch_bounds__(kT, 4) k_defl_emit(const uint8_t *__restrict__ src, uint64_t n, uint64_t blk0,
-                                                     const uint64_t *__restrict__ lmask, const uint8_t *__restrict__ nmatch,
-                                                     const uint32_t *__restrict__ mlist, const DeflTab *__restrict__ tabs,
-                                                     const uint32_t *__restrict__ zpow, const uint32_t *__restrict__ offs,
-                                                     const uint64_t *__restrict__ cbase, uint8_t *__restrict__ dst) {
-    __shared__ __align__(16) uint32_t img[kSlot / 4 + 4];
+// Two instances, chosen per block by its final size (T.total, known since k_defl_huff):
+//   CAP = kSlot          the image holds the largest BGZF block; 80,208 B of LDS, two workgroups per CU
+//   CAP = kEmitSmallCap  blocks of at most CAP bytes, three workgroups per CU.  The CRC's tables and
+//                        operators (8.3 KB, dead once the payload's CRC is in sh_crc) live in the image's
+//                        first words: tables -> CRC -> barrier -> image zeroed -> bit counts, scan, emission.
+// A block is small when total <= cap, the call's effective cap.  The small instance is launched over the chunk's
+// nb workgroups and a workgroup whose block is big returns at once; the big instance's workgroups walk the
+// list of big blocks k_scan_chunk wrote (big[0] of them, at big[4 ..]), or, without a list, take block
+// blockIdx.x when it is big.  The emission code (emit_block) is one body for both.
+struct EmitCrc {
+    uint32_t crctab[4][256];
+    uint32_t zp[17][32];
+    uint32_t zl[32][16];  // the CRC's per-lane combine operators (crc_combine512l)
+    uint32_t crcs[kT / 64];
+};
+constexpr uint32_t kLdsGranule = 1280;  // gfx950 allocates LDS in 320-dword granules
+constexpr uint32_t kLdsCu = 163840;
+// what an emit workgroup holds beside the image: ct, dist, scan, wsum, sh_crc, the big instance's crc word
+constexpr uint32_t kEmitFixed = (512 + kDist + kNSeg + kT / 64 + 2) * 4;
+constexpr uint32_t emit_lds(uint32_t cap) { return (cap + 16 + kEmitFixed + kLdsGranule - 1) / kLdsGranule * kLdsGranule; }
+#ifndef OGE_EMIT_SMALL_CAP  // the largest multiple of 1 KiB whose workgroup fits three times in a CU's LDS
+#define OGE_EMIT_SMALL_CAP (46 * 1024)
+#endif
+constexpr uint32_t kEmitSmallCap = OGE_EMIT_SMALL_CAP;
+static_assert(kEmitSmallCap % 1024 == 0 && 3 * emit_lds(kEmitSmallCap) <= kLdsCu && 3 * emit_lds(kEmitSmallCap + 1024) > kLdsCu,
+              "small emit instance: three workgroups per CU, and no larger cap does");
+static_assert(sizeof(EmitCrc) <= kEmitSmallCap, "the CRC tables alias the image");
+
+template <uint32_t CAP>
+__device__ __forceinline__ void emit_block(const uint32_t bi, const uint8_t *__restrict__ src, uint64_t n, uint64_t blk0,
+                                           const uint64_t *__restrict__ lmask, const uint8_t *__restrict__ nmatch,
+                                           const uint32_t *__restrict__ mlist, const DeflTab *__restrict__ tabs,
+                                           const uint32_t *__restrict__ zpow, const uint32_t *__restrict__ offs,
+                                           const uint64_t *__restrict__ cbase, uint8_t *__restrict__ dst) {
+    constexpr bool kSmall = CAP < kSlot;
+    const DeflTab &T = tabs[bi];
+    const uint32_t total = T.total, stored = T.stored, hb = T.hdr_bits;
+    __shared__ __align__(16) uint32_t img[CAP / 4 + 4];
     __shared__ uint32_t ct[512], dist[kDist];
     __shared__ uint32_t scan[kNSeg];
     __shared__ uint32_t wsum[kT / 64];
-    __shared__ uint32_t crctab[4][256];
-    __shared__ uint32_t zp[17][32];
-    __shared__ uint32_t zl[32][16];  // the CRC's per-lane combine operators (crc_combine512l)
-    __shared__ uint32_t crcs[kT / 64];
+    __shared__ __align__(16) uint32_t crc_own[kSmall ? 1 : sizeof(EmitCrc) / 4];
     __shared__ uint32_t sh_crc;
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const uint64_t blk = blk0 + blockIdx.x;
+    EmitCrc &C = *(EmitCrc *)(kSmall ? img : crc_own);
+    int tid = threadIdx.x;
+    // opaque per block: the big instance calls this in a loop, and with a loop-invariant thread index the compiler
+    // hoisted thread-derived values out of it and held them (128 VGPRs and 448 B of scratch; 94 and none so)
+    asm volatile("" : "+v"(tid));
+    const int t = tid, lane = t & 63, wv = t >> 6;
+    const uint64_t blk = blk0 + bi;
     const uint64_t start = blk * kPay;
     const uint32_t len = (uint32_t)min<uint64_t>(kPay, n - start);
     const uint8_t *s = src + start;
-    const DeflTab &T = tabs[blockIdx.x];
-    const uint32_t total = T.total, stored = T.stored, hb = T.hdr_bits;
     for (int i = t; i < 512; i += kT) ct[i] = ct_entry(i, T.lit);
     for (int i = t; i < kDist; i += kT) dist[i] = T.dist[i];
-    crc_setup<kT>(crctab, zp, zpow, t);
-    for (int i = t; i < 32 * 16; i += kT) zl[i >> 4][i & 15] = zpow[17 * 32 + i];
-    for (uint32_t i = t; i < (total + 15) / 16; i += kT) ((uint4 *)img)[i] = make_uint4(0, 0, 0, 0);
+    crc_setup<kT>(C.crctab, C.zp, zpow, t);
+    for (int i = t; i < 32 * 16; i += kT) C.zl[i >> 4][i & 15] = zpow[17 * 32 + i];
+    if (!kSmall)
+        for (uint32_t i = t; i < (total + 15) / 16; i += kT) ((uint4 *)img)[i] = make_uint4(0, 0, 0, 0);
     __syncthreads();
     {
-        const uint32_t c = crc_global512x4l(s, len, crctab, zl, zp, crcs, t);
+        const uint32_t c = crc_global512x4l(s, len, C.crctab, C.zl, C.zp, C.crcs, t);
         if (t == 0) sh_crc = c;
+    }
+    if (kSmall) {  // the tables are dead: their words become image, zeroed with the rest of it
+        __syncthreads();
+        for (uint32_t i = t; i < (total + 15) / 16; i += kT) ((uint4 *)img)[i] = make_uint4(0, 0, 0, 0);
+        if (stored) __syncthreads();  // (a deflate block's first image access follows the scan's barriers)
     }
     const uint32_t bsize = total - 1;
     if (stored) {
@@ -1447,10 +1486,10 @@ __global__ void __launch_bounds__(kT, 4) k_defl_emit(const uint8_t *__restrict__
     } else {
         // 1. the thread's two segments (sub-block 0 and 1): bytes, literal masks, bit counts
         const uint32_t s0a = t * kSeg, s0b = kSub + t * kSeg;
-        const uint64_t sga = (uint64_t)blockIdx.x * kNSeg + t, sgb = sga + kT;
+        const uint64_t sga = (uint64_t)bi * kNSeg + t, sgb = sga + kT;
         const uint64_t lma = s0a < len ? lmask[sga] : 0, lmb = s0b < len ? lmask[sgb] : 0;
         const uint32_t nma = s0a < len ? nmatch[sga] : 0, nmb = s0b < len ? nmatch[sgb] : 0;
-        const uint32_t *mpa = mlist + ((uint64_t)blockIdx.x * kMaxM) * kNSeg + t, *mpb = mpa + kT;
+        const uint32_t *mpa = mlist + ((uint64_t)bi * kMaxM) * kNSeg + t, *mpb = mpa + kT;
         // (the bytes and tokens are loaded again for the emit below -- L2 hits -- rather than held in
         // registers across the scan)
         uint32_t ca, cb;
@@ -1499,9 +1538,15 @@ __global__ void __launch_bounds__(kT, 4) k_defl_emit(const uint8_t *__restrict__
                 seg_emit(w, lma, nma, mpa, m, ct, dist, img, 144 + hb + scan[t]);
             }
             if (cb) {
+                // the second segment's mask is loaded again (an L2 hit, in flight beside the segment's bytes and
+                // tokens) through an index the compiler cannot tie to the first load: two registers not held
+                // across the emission above, which is what lets the small instance fit 80 VGPRs without scratch
+                uint32_t tb = t;
+                asm volatile("" : "+v"(tb));
+                const uint64_t lm2 = lmask[(uint64_t)bi * kNSeg + kT + tb];
                 seg_load(s, s0b, len, w);
                 seg_tokens(mpb, nmb, m);
-                seg_emit(w, lmb, nmb, mpb, m, ct, dist, img, 144 + hb + scan[kT + t]);
+                seg_emit(w, lm2, nmb, mpb, m, ct, dist, img, 144 + hb + scan[kT + t]);
             }
         }
         if (t == kT - 1) {  // end of block after the last segment
@@ -1531,7 +1576,7 @@ __global__ void __launch_bounds__(kT, 4) k_defl_emit(const uint8_t *__restrict__
     }
     __syncthreads();
     // 4. out at the block's final offset
-    uint8_t *D = dst + *cbase + offs[blockIdx.x];
+    uint8_t *D = dst + *cbase + offs[bi];
     const uint32_t sh = (uint32_t)((uintptr_t)D & 3);
     OGE_G uint32_t *A = (OGE_G uint32_t *)((uintptr_t)D & ~(uintptr_t)3);
     const uint32_t nwords = (total + sh + 3) / 4;
@@ -1548,40 +1593,74 @@ __global__ void __launch_bounds__(kT, 4) k_defl_emit(const uint8_t *__restrict__
     }
 }
 
+template <uint32_t CAP>
+__global__ void __launch_bounds__(kT, CAP < kSlot ? 6 : 4) k_defl_emit(const uint8_t *__restrict__ src, uint64_t n, uint64_t blk0,
+                                                     const uint64_t *__restrict__ lmask, const uint8_t *__restrict__ nmatch,
+                                                     const uint32_t *__restrict__ mlist, const DeflTab *__restrict__ tabs,
+                                                     const uint32_t *__restrict__ zpow, const uint32_t *__restrict__ offs,
+                                                     const uint64_t *__restrict__ cbase, uint8_t *__restrict__ dst, uint32_t cap,
+                                                     const uint32_t *__restrict__ big) {
+    if (CAP < kSlot) {
+        if (tabs[blockIdx.x].total <= cap) emit_block<CAP>(blockIdx.x, src, n, blk0, lmask, nmatch, mlist, tabs, zpow, offs, cbase, dst);
+    } else {
+        const uint32_t nq = big ? big[0] : blockIdx.x + 1;
+#pragma unroll 1
+        for (uint32_t q = blockIdx.x; q < nq; q += gridDim.x) {
+            const uint32_t bi = big ? big[4 + q] : q;
+            if (!big && tabs[bi].total <= cap) break;
+            emit_block<CAP>(bi, src, n, blk0, lmask, nmatch, mlist, tabs, zpow, offs, cbase, dst);
+            __syncthreads();
+        }
+    }
+}
+
 // exclusive scan of n <= kMaxChunk block sizes, one 1024-thread workgroup, kPer consecutive entries per
 // thread (the per-chunk offsets; runs on the chunk's own stream)
 constexpr uint32_t kMaxChunk = 16384, kPer = kMaxChunk / 1024;
-__global__ void __launch_bounds__(1024) k_scan_chunk(const uint32_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ out) {
-    __shared__ uint32_t ws[16];
+// Also sorts out the emit classes: the chunk's blocks of the small class (size <= cap) are counted into *nsmall,
+// the word next to the stream's running end (one atomic per wave that has any), and the others are listed
+// in block order in big[4 ..], their number in big[0] (what the big emit instance's workgroups walk).
+__global__ void __launch_bounds__(1024) k_scan_chunk(const uint32_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ out,
+                                                     uint32_t cap, unsigned long long *__restrict__ nsmall,
+                                                     uint32_t *__restrict__ big) {
+    __shared__ uint32_t ws[16], wb[16];
     const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
-    uint32_t a[kPer], v = 0;
+    uint32_t a[kPer], v = 0, nbig = 0, small = 0;
 #pragma unroll
     for (uint32_t i = 0; i < kPer; ++i) {
         a[i] = kPer * t + i < n ? in[kPer * t + i] : 0;
         v += a[i];
+        small += a[i] && a[i] <= cap;
+        nbig += a[i] > cap;
     }
-    uint32_t x = v;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) small += __shfl_xor(small, d, 64);
+    if (lane == 0 && small) atomicAdd(nsmall, (unsigned long long)small);
+    uint32_t x = v, xb = nbig;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= (uint32_t)d) x += y;
+        const uint32_t y = __shfl_up(x, d, 64), yb = __shfl_up(xb, d, 64);
+        if (lane >= (uint32_t)d) x += y, xb += yb;
     }
-    if (lane == 63) ws[w] = x;
+    if (lane == 63) ws[w] = x, wb[w] = xb;
     __syncthreads();
     if (t < 16) {
-        uint32_t s = ws[t], z = s;
+        uint32_t s = ws[t], z = s, sb = wb[t], zb = sb;
         for (int d = 1; d < 16; d <<= 1) {
-            const uint32_t y = __shfl_up(z, d, 16);
-            if ((t & 15) >= (uint32_t)d) z += y;
+            const uint32_t y = __shfl_up(z, d, 16), yb = __shfl_up(zb, d, 16);
+            if ((t & 15) >= (uint32_t)d) z += y, zb += yb;
         }
         ws[t] = z - s;
+        wb[t] = zb - sb;
+        if (t == 15) big[0] = zb;
     }
     __syncthreads();
-    uint32_t excl = ws[w] + x - v;
+    uint32_t excl = ws[w] + x - v, rank = wb[w] + xb - nbig;
 #pragma unroll
     for (uint32_t i = 0; i < kPer; ++i) {
         if (kPer * t + i < n) out[kPer * t + i] = excl;
         excl += a[i];
+        if (a[i] > cap) big[4 + rank++] = kPer * t + i;
     }
 }
 
@@ -1606,6 +1685,17 @@ __global__ void k_fix_bins(uint8_t *__restrict__ recs, const uint64_t *__restric
 
 
 extern "C" uint64_t oge_bgzf_bound(uint64_t n) { return ((n + kPay - 1) / kPay) * (uint64_t)kSlot; }
+
+// the compiled cap of the small emit instance (bytes of a whole BGZF block)
+extern "C" uint32_t oge_defl_emit_cap(void) { return kEmitSmallCap; }
+
+// The call's effective cap: OGE_DEFL_EMIT_CAP in bytes, read per call.  Unset: the compiled cap; 0: every
+// block to the big instance; values above the compiled cap are clamped to it.
+static uint32_t emit_cap_now() {
+    const char *e = getenv("OGE_DEFL_EMIT_CAP");
+    if (!e || !*e) return kEmitSmallCap;
+    return (uint32_t)std::min<unsigned long long>(strtoull(e, nullptr, 10), kEmitSmallCap);
+}
 
 extern "C" int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t n, int level, uint8_t *d_dst,
                                     uint64_t dst_cap, uint64_t *out_bytes) {
@@ -1656,7 +1746,7 @@ extern "C" int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t
     const int S = nblk > chunk ? OGE_DEFL_STREAMS : 1;
     struct Bufs {
         uint64_t *lmask, *cbase;
-        uint32_t *mlist, *freq, *sizes, *offs;
+        uint32_t *mlist, *freq, *sizes, *offs, *big;
         uint8_t *nmatch;
         DeflTab *tabs;
         hipStream_t st;
@@ -1671,9 +1761,10 @@ extern "C" int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t
         B[s].sizes = (uint32_t *)ctx->ws(("defl_sizes" + x).c_str(), chunk * 4 + 16);
         B[s].offs = (uint32_t *)ctx->ws(("defl_offs" + x).c_str(), chunk * 4 + 16);
         B[s].cbase = (uint64_t *)ctx->ws(("defl_cbase" + x).c_str(), 16);
+        B[s].big = (uint32_t *)ctx->ws(("defl_big" + x).c_str(), chunk * 4 + 16);  // [0] the count, [4 ..] the blocks
         B[s].st = S == 1 ? ctx->stream : ctx->side_stream(s);
         if (!B[s].lmask || !B[s].nmatch || !B[s].mlist || !B[s].freq || !B[s].tabs || !B[s].sizes || !B[s].offs ||
-            !B[s].cbase || !B[s].st)
+            !B[s].cbase || !B[s].big || !B[s].st)
             return OGE_ERR_HIP;
     }
     // the 2^k zero-byte operators, then the emit's 16-lane combine operators (crc_zlane, 128-byte pieces)
@@ -1689,7 +1780,8 @@ extern "C" int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t
         return v;
     }();
     OGE_HIP_TRY(ctx, hipMemcpyAsync(zpow, &zh, sizeof(zh), hipMemcpyHostToDevice, ctx->stream));
-    OGE_HIP_TRY(ctx, hipMemsetAsync(base, 0, 8, ctx->stream));
+    OGE_HIP_TRY(ctx, hipMemsetAsync(base, 0, 16, ctx->stream));  // the stream's running end, the small-class block count
+    const uint32_t ecap = emit_cap_now();
     OgeStage stage(ctx, "bgzf_deflate");
     hipEvent_t ev[4];
     for (auto &e : ev) OGE_HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1723,13 +1815,26 @@ extern "C" int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t
         OGE_LAUNCH_CHECK(ctx);
         k_defl_huff<<<nb, 64, 0, u.st>>>(u.freq, u.tabs, n, b0, level, u.sizes);
         OGE_LAUNCH_CHECK(ctx);
-        k_scan_chunk<<<1, 1024, 0, u.st>>>(u.sizes, nb, u.offs);
+        k_scan_chunk<<<1, 1024, 0, u.st>>>(u.sizes, nb, u.offs, ecap, (unsigned long long *)(base + 1), u.big);
         OGE_LAUNCH_CHECK(ctx);
         if (k) OGE_HIP_TRY(ctx, hipStreamWaitEvent(u.st, ev[(k - 1) % S], 0));  // previous chunk's offset advance
         k_defl_advance<<<1, 64, 0, u.st>>>(base, u.cbase, u.offs, u.sizes, nb);
         OGE_LAUNCH_CHECK(ctx);
         OGE_HIP_TRY(ctx, hipEventRecord(ev[k % S], u.st));
-        k_defl_emit<<<nb, kT, 0, u.st>>>(d_src, n, b0, u.lmask, u.nmatch, u.mlist, u.tabs, zpow, u.offs, u.cbase, d_dst);
+        // The small instance over the chunk's blocks: a workgroup whose block is of the big class returns at once.
+        // The big one as two workgroups per CU that walk the list k_scan_chunk made: even a workgroup with
+        // nothing to do waits for 80 KB of free LDS beside the other streams' kernels, and nb of them after every
+        // chunk of small blocks held the stream back (300M chain: deflate 360.4 ms, with the list 356.8).  The
+        // two write disjoint ranges of the output.  Cap 0: no small class, one big workgroup per block as before.
+        if (ecap) {
+            k_defl_emit<kEmitSmallCap><<<nb, kT, 0, u.st>>>(d_src, n, b0, u.lmask, u.nmatch, u.mlist, u.tabs, zpow, u.offs, u.cbase,
+                                                            d_dst, ecap, nullptr);
+            OGE_LAUNCH_CHECK(ctx);
+            k_defl_emit<kSlot><<<std::min<uint32_t>(nb, 2 * (uint32_t)ncu), kT, 0, u.st>>>(d_src, n, b0, u.lmask, u.nmatch, u.mlist, u.tabs,
+                                                                                           zpow, u.offs, u.cbase, d_dst, ecap, u.big);
+        } else {
+            k_defl_emit<kSlot><<<nb, kT, 0, u.st>>>(d_src, n, b0, u.lmask, u.nmatch, u.mlist, u.tabs, zpow, u.offs, u.cbase, d_dst, 0, nullptr);
+        }
         OGE_LAUNCH_CHECK(ctx);
     }
     // every chunk's emit: the context stream waits for all side streams
@@ -1740,10 +1845,16 @@ extern "C" int oge_bgzf_deflate_dev(oge_ctx *ctx, const uint8_t *d_src, uint64_t
         }
     }
     stage.end();
-    uint64_t total = 0;
-    OGE_HIP_TRY(ctx, hipMemcpyAsync(&total, base, 8, hipMemcpyDeviceToHost, ctx->stream));
+    uint64_t total[2] = {0, 0};  // the stream's bytes, its small-class blocks
+    OGE_HIP_TRY(ctx, hipMemcpyAsync(total, base, 16, hipMemcpyDeviceToHost, ctx->stream));
     OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *out_bytes = total;
+    *out_bytes = total[0];
+    ctx->counters["defl_emit_small"] += total[1];
+    ctx->counters["defl_emit_big"] += nblk - total[1];
+    static const bool tr = getenv("OGE_TRACE_DEFL") != nullptr;
+    if (tr)
+        fprintf(stderr, "[oge defl] %llu blocks, %llu bytes, emit cap %u: %llu small, %llu big\n", (unsigned long long)nblk,
+                (unsigned long long)total[0], ecap, (unsigned long long)total[1], (unsigned long long)(nblk - total[1]));
     return OGE_OK;
 }
 

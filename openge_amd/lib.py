@@ -322,6 +322,7 @@ def lib() -> C.CDLL:
         "oge_realign_synth_defaults": (None, [vp]),
         "oge_synth_realign": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
         "oge_bgzf_bound": (u64, [u64]),
+        "oge_defl_emit_cap": (u32, []),
         "oge_bgzf_deflate_dev": (C.c_int, [vp, vp, u64, C.c_int, vp, u64, C.POINTER(u64)]),
         "oge_bgzf_deflate": (C.c_int, [vp, vp, u64, C.c_int, vp, u64, C.POINTER(u64)]),
         "oge_fix_bins_dev": (C.c_int, [vp, vp, vp, u64]),

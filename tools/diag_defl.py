@@ -28,7 +28,9 @@ for _ in range(4):
     zb = ctx.bgzf_deflate_dev(d_recs.data_ptr(), B, level, d_z.data_ptr(), cap)
     ms.append(round(ctx.timing("bgzf_deflate"), 2))
 sha = hashlib.sha256(d_z[:zb].cpu().numpy().tobytes()).hexdigest()[:16]
-print(sys.argv[1:] or ["default"], "level", level, "deflate ms", ms[1:], "bytes", zb, "ratio", round(zb / B, 4), "sha", sha, flush=True)
+cls = {k: ctx.counter("defl_emit_" + k) for k in ("small", "big")}  # blocks per emit instance (None: a build without them)
+print(sys.argv[1:] or ["default"], "reads", n, "level", level, "emit cap", os.environ.get("OGE_DEFL_EMIT_CAP", "compiled"),
+      "deflate ms", ms[1:], "bytes", zb, "ratio", round(zb / B, 4), "blocks", cls, "sha", sha, flush=True)
 if os.environ.get("DIAG_ZLIB"):  # zlib level 6 per 65,280-byte payload over the first 32 MiB, for comparison
     import zlib
     h = d_recs[: 65280 * 514].cpu().numpy().tobytes()
