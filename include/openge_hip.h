@@ -656,6 +656,67 @@ int oge_compare(oge_ctx *ctx, const uint8_t *recs_a, uint64_t rec_bytes_a, const
                 const oge_compare_region *region, uint32_t want, int debug_hash_bits, oge_compare_result *result,
                 uint8_t *diff_out, uint64_t cap, uint64_t *diff_bytes);
 
+/* ---- realignment target intervals of records in HBM (openge targets, localrealign --auto-targets) --------
+ * The intervals oge_localrealign takes as its intervals file, computed from the reads' own indels: GATK's
+ * RealignerTargetCreator at its defaults without mismatch-entropy events and known indels (the reference has no
+ * such step, algorithms/local_realignment.cpp:75-100); DESIGN.md section 25.  Coordinates are 1-based and closed.
+ * Reads used: FLAG has none of 0x4, 0x100, 0x200, 0x400; MAPQ is neither 0 nor 255; refID >= 0 and pos >= 0; not
+ * a bad mate (FLAG 0x1 set, 0x8 clear, mate refID != refID).
+ * Events: first / last = the read's first and last M, = or X op (none: no event); every I or D op at an index
+ * strictly between them is an event at a = pos + the lengths of the M, D, N, = and X ops before it (pos the raw
+ * 0-based BAM position, so a is the 1-based base just before the indel): an insertion gives (refID, a, a + 1), a
+ * deletion of length L (refID, a, a + L); adjacent I and D ops both count, N and P never.  The stop is clipped to
+ * the contig's length (a length below 0 counts as 0); a is computed in 64 bits and stored as min(a, 2^31 - 1).
+ * Merge: the events in (refID, start, stop) order; an event joins the current interval when it has its refID and
+ * start <= the interval's stop + gap, the stop becomes the larger one; otherwise it opens an interval.  n_events
+ * = the events that joined.  Drop: an interval with stop - start >= max_interval is left out and counted.
+ * Output: the kept intervals in (refID, start) order as oge_target records and, with OGE_TARGETS_TEXT, as lines
+ * "contig:start-stop\n" (always both numbers: what the realigner's intervals parser reads).  The order of the
+ * input records does not matter.
+ * Result: reads_used, events, intervals (before the drop), dropped_long, targets (= intervals - dropped_long),
+ * text_bytes (0 without OGE_TARGETS_TEXT).
+ * OGE_ERR_ARG (the message names the lowest such record, and of that record the first of the three): a read that
+ * passes the filter with refID >= n_ref, with a CIGAR that does not fit its block_size, or with a CIGAR op code
+ * above 8; max_interval < 1, gap < 0, n_ref < 0, unknown want bits, names that are not n_ref NUL-terminated
+ * strings.  OGE_ERR_LIMIT: events >= 2^32 - 1.
+ * Counters (oge_ctx_counter): "targets_tile_records" = the records one workgroup of the event pass takes per
+ * append, "targets_merge_tile" = the sorted events one workgroup of the running maximum takes, "targets_events".
+ * Stage name for oge_ctx_timing: "targets"; nested in it "targets_count", "targets_events", "targets_sort",
+ * "targets_merge" (with the drop and the compaction) and "targets_text". */
+typedef struct oge_targets_opts {
+    int32_t max_interval; /* 500 (GATK's maxIntervalSize) */
+    int32_t gap;          /* 0: touching or overlapping events merge */
+    uint32_t want;        /* OGE_TARGETS_TEXT */
+} oge_targets_opts;
+void oge_targets_opts_init(oge_targets_opts *o);
+typedef struct oge_targets_result {
+    uint64_t reads_used, events, intervals, dropped_long, targets, text_bytes;
+} oge_targets_result;
+typedef struct oge_target {
+    int32_t ref_id, start, stop;
+    uint32_t n_events;
+} oge_target;
+enum { OGE_TARGETS_TEXT = 1 };
+/* Records d_recs + d_off[i] (n offsets; the arena carries 16 bytes of slack behind the last record).  The
+ * dictionary is the host's: ref_len (n_ref entries) and ref_names, the n_ref names one after the other, each
+ * NUL-terminated, names_bytes bytes in all (as oge_ctx_last_refs hands them out; read only with
+ * OGE_TARGETS_TEXT).  *d_targets (device, result->targets entries) and *d_text (device, result->text_bytes
+ * bytes; d_text may be NULL without OGE_TARGETS_TEXT) are valid until the next call on ctx; NULL when empty. */
+int oge_targets_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref,
+                    const int32_t *ref_len, const char *ref_names, uint64_t names_bytes, const oge_targets_opts *opts,
+                    oge_targets_result *result, const oge_target **d_targets, const uint8_t **d_text);
+/* Host-buffer form: uploads, computes, copies the records into targets_out (targets_cap entries) and the text into
+ * text_out (text_cap bytes); OGE_ERR_LIMIT with *result filled when either is too small, so a first call with
+ * both caps 0 sizes the buffers. */
+int oge_targets(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const uint64_t *rec_off, uint64_t n, int32_t n_ref,
+                const int32_t *ref_len, const char *ref_names, uint64_t names_bytes, const oge_targets_opts *opts,
+                oge_targets_result *result, oge_target *targets_out, uint64_t targets_cap, uint8_t *text_out,
+                uint64_t text_cap);
+/* A whole BAM file resident in HBM (4-byte aligned): framing index, inflate, header, record walk, then the
+ * targets against the file's own reference list (which stays with the context for oge_ctx_last_refs). */
+int oge_bam_targets_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const oge_targets_opts *opts,
+                        oge_targets_result *result, const oge_target **d_targets, const uint8_t **d_text);
+
 /* ---- SAM and FASTQ text of records in HBM (openge view, -F sam|fastq) ----------------------------------
  * The reference's SamWriter::write (util/sam_writer.cpp:90-217) and the single-stream form of
  * FastqWriter::write (util/fastq_writer.cpp:99-100) on the device; DESIGN.md section 21.

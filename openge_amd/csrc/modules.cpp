@@ -1281,8 +1281,79 @@ static int realign_ranks(ChainContext &cc, ReadBatch &b, const std::string &ht, 
     return 0;
 }
 
+static void report_targets(const oge_targets_result &r, int max_interval, int gap);
+static int write_text_file(const std::string &out, const std::vector<uint8_t> &text);
+
+// --auto-targets: the intervals of `openge targets` at its defaults, from the batch where it lies (the device
+// form when it is valid, else through the host form), written to <tmpdir>/oge_targets_<pid>.intervals.
+// *n_targets = 0: nothing to realign, no file.
+int LocalRealignment::auto_targets(ChainContext &cc, ReadBatch &b, std::string &path, uint64_t *n_targets) {
+    const size_t n_ref = b.ref_names.size();
+    if (b.header.sq.size() != n_ref) {
+        fprintf(stderr, "openge localrealign: --auto-targets needs a header whose @SQ lines match the reference list\n");
+        return -1;
+    }
+    std::vector<int32_t> lens;
+    std::string names;
+    for (size_t r = 0; r < n_ref; ++r) {
+        lens.push_back((int32_t)std::min<long long>(std::max<long long>(b.header.sq[r].length, 0), INT32_MAX));
+        names.append(b.ref_names[r].c_str(), b.ref_names[r].size() + 1);
+    }
+    oge_targets_opts o;
+    oge_targets_opts_init(&o);
+    oge_targets_result res;
+    std::vector<uint8_t> text;
+    int rc;
+    if (b.dev_valid) {
+        const oge_target *d_targets = nullptr;
+        const uint8_t *d_text = nullptr;
+        rc = oge_targets_dev(cc.ctx, b.d_recs, b.d_offs, b.n, (int32_t)n_ref, lens.data(), names.data(), names.size(), &o, &res, &d_targets,
+                             &d_text);
+        if (!rc && res.text_bytes) {
+            text.resize(res.text_bytes);
+            rc = oge_memcpy(cc.ctx, text.data(), d_text, res.text_bytes, 2);
+        }
+    } else {
+        if (cc.to_host(b)) return -1;
+        std::vector<oge_target> tg;
+        const uint64_t bytes = b.n ? b.offs[b.n] : 0;
+        auto call = [&]() {
+            return oge_targets(cc.ctx, b.recs.data(), bytes, b.offs.data(), b.n, (int32_t)n_ref, lens.data(), names.data(), names.size(), &o, &res,
+                               tg.data(), tg.size(), text.data(), text.size());
+        };
+        rc = call();  // sizes the outputs
+        if (rc == OGE_ERR_LIMIT && res.targets) {
+            tg.resize(res.targets);
+            text.resize(res.text_bytes);
+            rc = call();
+        }
+    }
+    if (rc) return cc.fail("LocalRealignment: targets");
+    if (verbose) report_targets(res, o.max_interval, o.gap);
+    *n_targets = res.targets;
+    if (!res.targets) return 0;
+    path = tmpdir_ + (tmpdir_.empty() || tmpdir_.back() == '/' ? "" : "/") + "oge_targets_" + std::to_string((long long)getpid()) + ".intervals";
+    return write_text_file(path, text);
+}
+
 int LocalRealignment::runInternal(ChainContext &cc, ReadBatch &b) {
     const auto t0 = clk();
+    // the computed intervals file lives until the realigner has read it
+    struct TempFile {
+        std::string path;
+        ~TempFile() {
+            if (!path.empty()) remove(path.c_str());
+        }
+    } temp;
+    if (auto_targets_) {
+        uint64_t n_targets = 0;
+        if (auto_targets(cc, b, temp.path, &n_targets)) return -1;
+        if (!n_targets) {  // the realigner's parser refuses an empty file: the records pass through as they are
+            if (verbose) fprintf(stderr, "[openge] LocalRealignment: no targets, the records pass through unchanged\n");
+            return 0;
+        }
+        intervals_ = temp.path;
+    }
     if (cc.to_host(b)) return -1;
     cc.free_device(b);
     const std::string ht = b.header.to_string();
@@ -1933,6 +2004,12 @@ struct QcInput {
         if (sam) return *n = b.n, 0;
         return oge_bam_count_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, n);
     }
+    int targets(const oge_targets_opts *o, oge_targets_result *res, const oge_target **d_targets, const uint8_t **d_text) {
+        if (!sam) return oge_bam_targets_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, o, res, d_targets, d_text);
+        for (auto &nm : b.ref_names) sam_names.append(nm.c_str(), nm.size() + 1);
+        return oge_targets_dev(cc.ctx, b.d_recs, b.d_offs, b.n, (int32_t)sam_lens.size(), sam_lens.data(), sam_names.data(), sam_names.size(), o,
+                               res, d_targets, d_text);
+    }
     int coverage(int32_t binsize, const uint32_t **d_bins, uint64_t *nb, uint64_t *skipped, int32_t *overflow, int32_t *n_ref, const char **names,
                  const int32_t **lens) {
         if (!sam) {
@@ -2065,6 +2142,56 @@ int count_bam_file(ChainContext &cc, const std::string &path) {
         fprintf(stderr, "openge: error writing to stdout\n");
         return -1;
     }
+    return 0;
+}
+
+static void report_targets(const oge_targets_result &r, int max_interval, int gap) {
+    fprintf(stderr, "[openge] targets: %llu reads used, %llu events, %llu intervals, %llu dropped (--maxinterval %d), %llu targets (--gap %d), %llu bytes of text\n",
+            (unsigned long long)r.reads_used, (unsigned long long)r.events, (unsigned long long)r.intervals, (unsigned long long)r.dropped_long,
+            max_interval, (unsigned long long)r.targets, gap, (unsigned long long)r.text_bytes);
+}
+
+static int write_text_file(const std::string &out, const std::vector<uint8_t> &text) {
+    FILE *f = fopen(out.c_str(), "wb");
+    const bool ok = f && fwrite(text.data(), 1, text.size(), f) == text.size();
+    if ((f && fclose(f) != 0) || !ok) {
+        fprintf(stderr, "openge: error writing %s: %s\n", out.c_str(), strerror(errno));
+        remove(out.c_str());
+        return -1;
+    }
+    return 0;
+}
+
+int targets_bam_file(ChainContext &cc, const std::string &path, const std::string &out, int max_interval, int gap) {
+    QcInput in(cc);
+    if (in.load(path)) return -1;
+    oge_targets_opts o;
+    oge_targets_opts_init(&o);
+    o.max_interval = max_interval;
+    o.gap = gap;
+    oge_targets_result res;
+    const oge_target *d_targets = nullptr;
+    const uint8_t *d_text = nullptr;
+    std::vector<uint8_t> text;
+    int rc = in.targets(&o, &res, &d_targets, &d_text);
+    if (!rc && res.text_bytes) {
+        text.resize(res.text_bytes);
+        rc = oge_memcpy(cc.ctx, text.data(), d_text, res.text_bytes, 2);
+    }
+    in.z.buf.reset();
+    if (rc) return cc.fail("targets");
+    const auto t0 = clk();
+    if (out == "stdout" || out == "-") {
+        const bool ok = fwrite(text.data(), 1, text.size(), stdout) == text.size() && fflush(stdout) == 0 && !ferror(stdout);
+        if (!ok) {
+            fprintf(stderr, "openge: error writing to stdout\n");
+            return -1;
+        }
+    } else if (write_text_file(out, text)) {
+        return -1;
+    }
+    if (cc.verbose) report_targets(res, max_interval, gap);
+    report_stages(cc, "targets", sec(t0, clk()));
     return 0;
 }
 

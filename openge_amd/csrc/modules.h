@@ -232,9 +232,14 @@ public:
     bool verbose = false;
     void setReferenceFilename(const std::string &f) { reference_ = f; }
     void setIntervalsFilename(const std::string &f) { intervals_ = f; }
+    // --auto-targets: the intervals are computed from the batch (oge_targets_dev at its defaults) and handed to the
+    // realigner through a file in tmpdir that is removed afterwards; no targets: the records pass through
+    void setAutoTargets(bool on, const std::string &tmpdir) { auto_targets_ = on; tmpdir_ = tmpdir; }
 protected:
     int runInternal(ChainContext &cc, ReadBatch &b) override;
-    std::string reference_, intervals_;
+    int auto_targets(ChainContext &cc, ReadBatch &b, std::string &path, uint64_t *n_targets);
+    std::string reference_, intervals_, tmpdir_ = "/tmp";
+    bool auto_targets_ = false;
 };
 
 // The multi-GPU form of ReadSorter (+ MarkDuplicates) and of a standalone MarkDuplicates: the batch
@@ -293,6 +298,11 @@ int index_bam_file(ChainContext &cc, const std::string &path, const std::string 
 int stats_bam_file(ChainContext &cc, const std::string &path, bool inserts, bool lengths);
 int count_bam_file(ChainContext &cc, const std::string &path);
 int coverage_bam_file(ChainContext &cc, const std::string &path, const std::string &out, int binsize, bool omit_uncovered);
+
+// `openge targets [-o out.intervals] [--maxinterval N] [--gap N] in.bam|in.sam`: the file into HBM through the
+// same loader, one call (oge_bam_targets_dev, or oge_targets_dev on the records of a SAM file), the text as the
+// device wrote it to out ("stdout": standard output)
+int targets_bam_file(ChainContext &cc, const std::string &path, const std::string &out, int max_interval, int gap);
 
 // `openge compare [-r REGION]... [-p] ref.bam other.bam [more...]` (commands/command_compare.cpp): every input
 // through a FileReader into its own batch in HBM, file 0 resident while the others come and go; the regions

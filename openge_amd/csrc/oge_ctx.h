@@ -81,6 +81,7 @@ struct oge_ctx {
     // last oge_sam_parse call returned (host memory, valid until the next one)
     OgeContigTable text_table{"text_names", "text_name_off", nullptr, "text_table_uploads"};
     OgeContigTable sam_table{"sam_names", "sam_name_off", "sam_slots", "sam_table_uploads"};
+    OgeContigTable targets_table{"tg_names", "tg_name_off", nullptr, "targets_table_uploads"};  // oge_targets_dev's
     std::vector<uint8_t> sam_out_recs, sam_out_warn;
     std::vector<uint64_t> sam_out_off;
     std::map<std::string, uint64_t> counters;  // per call: work counts a stage reports (oge_ctx_counter)
@@ -228,6 +229,12 @@ int oge_qc_stats_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off
                       const uint32_t **d_len, const uint64_t **d_len_count);
 int oge_qc_coverage_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref, const int32_t *ref_len,
                          int32_t binsize, const uint32_t **d_bins, uint64_t *n_skipped, int32_t *overflow);
+
+// ---- realignment targets (targets.hip) ----
+// oge_targets_dev without the context checks and the timing reset (oge_bam_targets_dev calls it under its hold)
+int oge_targets_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref, const int32_t *ref_len,
+                     const char *ref_names, uint64_t names_bytes, const oge_targets_opts *opts, oge_targets_result *result,
+                     const oge_target **d_targets, const uint8_t **d_text);
 
 // ---- multi-GPU internals (dist.hip)
 oge_ctx *oge_comm_ctx(oge_comm *comm);

@@ -14,6 +14,9 @@
 // command_count.cpp, command_coverage.cpp for the last three).
 // `compare` loads every input into HBM and takes the multiset difference of the read placements there
 // (compare_files in modules.cpp, csrc/compare.hip; commands/command_compare.cpp).
+// `targets` (not in the reference, whose comments send the user to GATK's RealignerTargetCreator) computes the
+// intervals file localrealign -L takes from the reads' own indels (targets_bam_file, csrc/targets.hip; DESIGN.md
+// section 25); `localrealign --auto-targets` computes the same intervals from the records it is handed.
 //
 // Deliberate differences: view -B/-E cuts QUAL to the window of SEQ; the reference cuts the
 // qualities of the already shortened read a second time (algorithms/filter.cpp:188-189), which leaves fewer
@@ -77,7 +80,8 @@ const Opt kStats[] = {{"I", "inserts", false}, {"L", "lengths", false}};
 const Opt kCoverage[] = {{"o", "out", true}, {"b", "binsize", true}, {"", "omituncoveredbases", false},
                          {"V", "verifymapping", false}, {"S", "strict", false}};
 const Opt kCompare[] = {{"r", "region", true}, {"p", "print", false}};
-const Opt kRealign[] = {{"o", "out", true}, {"R", "reference", true}, {"L", "intervals", true}};
+const Opt kTargets[] = {{"o", "out", true}, {"", "maxinterval", true}, {"", "gap", true}};
+const Opt kRealign[] = {{"o", "out", true}, {"R", "reference", true}, {"L", "intervals", true}, {"", "auto-targets", false}};
 
 struct Parsed {
     std::map<std::string, std::vector<std::string>> vm;  // long name -> values ("" for flags)
@@ -137,7 +141,7 @@ bool parse(int argc, const char **argv, const std::vector<Opt> &opts, Parsed &p)
 
 void usage_top() {
     fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, view, index, stats, count, coverage,\n"
-                    "          compare, version\n"
+                    "          compare, targets, version\n"
                     "\n    Inputs are BAM files or SAM text (first byte '@'; also on stdin, and mixed with BAM files); SAM is parsed\n"
                     "    on the GPU.  index takes BAM only.\n"
                     "\n    openge view [-o out] [-n N] [-q MAPQ] [-l LEN] [-r REGION] [-L FILE] [-B N] [-E N] in.bam|in.sam\n"
@@ -163,6 +167,14 @@ void usage_top() {
                     "                                        read placements (contig, position, CIGAR) of every later file that\n"
                     "                                        the first one lacks (added) or has more of (removed), per region\n"
                     "                                        (reads that START in it); -p prints each one; one GPU, no stdin\n"
+                    "    openge targets [-o out.intervals] [--maxinterval N] [--gap N] in.bam|in.sam\n"
+                    "                                        realignment target intervals (contig:start-stop) from the reads' own\n"
+                    "                                        indels, computed on the GPU: events closer than --gap (default 0) merge,\n"
+                    "                                        intervals of --maxinterval (default 500) bases or more are dropped;\n"
+                    "                                        the file localrealign -L takes; one file, one GPU, no stdin\n"
+                    "    openge localrealign -R ref.fa (-L targets.intervals | --auto-targets) [-T tmpdir] [-o out.bam] in.bam\n"
+                    "                                        --auto-targets: the intervals of `openge targets` at its defaults,\n"
+                    "                                        computed from the input's records (kept in a file in tmpdir meanwhile)\n"
                     "\nGPU options (every command):\n"
                     "    --device N              first GPU\n"
                     "    --gpus G                ranks over G GPUs\n"
@@ -197,6 +209,7 @@ int main(int argc, const char **argv) {
     else if (cmd == "count") ;  // no options of its own (commands/command_count.cpp)
     else if (cmd == "coverage") opts.insert(opts.end(), std::begin(kCoverage), std::end(kCoverage));
     else if (cmd == "compare") opts.insert(opts.end(), std::begin(kCompare), std::end(kCompare));
+    else if (cmd == "targets") opts.insert(opts.end(), std::begin(kTargets), std::end(kTargets));
     else {
         fprintf(stderr, "Unknown command %s.\n", argv[1]);
         return -1;
@@ -324,6 +337,28 @@ int main(int argc, const char **argv) {
             return -1;
         }
     }
+    if (cmd == "targets") {  // refused before anything is read
+        if (p.inputs.size() != 1 || p.inputs[0] == "stdin" || p.inputs[0] == "-") {
+            fprintf(stderr, "openge targets: one BAM or SAM file is required (stdin is not provided)\n");
+            return -1;
+        }
+        if (cc.gpus > 1) {
+            fprintf(stderr, "openge targets: --gpus is not provided\n");
+            return -1;
+        }
+        if (atoi(p.get("maxinterval", "500").c_str()) < 1) {
+            fprintf(stderr, "openge targets: --maxinterval must be at least 1\n");
+            return -1;
+        }
+        if (atoi(p.get("gap", "0").c_str()) < 0) {
+            fprintf(stderr, "openge targets: --gap must not be negative\n");
+            return -1;
+        }
+    }
+    if (cmd == "localrealign" && p.count("auto-targets") && p.count("intervals")) {
+        fprintf(stderr, "openge localrealign: -L and --auto-targets exclude each other\n");
+        return -1;
+    }
     if (p.count("regions")) {  // an unreadable -L file is refused before anything is read
         const std::string rf = p.get("regions", "");
         FILE *f = fopen(rf.c_str(), "r");
@@ -357,6 +392,12 @@ int main(int argc, const char **argv) {
     }
     if (cmd == "compare") {
         const int r = compare_files(cc, p.inputs, p.count("region") ? p.vm["region"] : std::vector<std::string>(), p.count("print"));
+        oge_ctx_destroy(cc.ctx);
+        return r;
+    }
+    if (cmd == "targets") {
+        const int r = targets_bam_file(cc, p.inputs[0], p.get("out", "stdout"), atoi(p.get("maxinterval", "500").c_str()),
+                                       atoi(p.get("gap", "0").c_str()));
         oge_ctx_destroy(cc.ctx);
         return r;
     }
@@ -436,7 +477,8 @@ int main(int argc, const char **argv) {
             fprintf(stderr, "One FASTA reference file is required.\n");
             return -1;
         }
-        if (!p.count("intervals") || p.vm["intervals"].size() != 1) {
+        const bool auto_targets = p.count("auto-targets");
+        if (!auto_targets && (!p.count("intervals") || p.vm["intervals"].size() != 1)) {
             fprintf(stderr, "One intervals file is required.\n");
             return -1;
         }
@@ -444,6 +486,7 @@ int main(int argc, const char **argv) {
         lr.verbose = cc.verbose;
         lr.setReferenceFilename(p.get("reference", ""));
         lr.setIntervalsFilename(p.get("intervals", ""));
+        lr.setAutoTargets(auto_targets, p.get("tmpdir", "/tmp"));
         reader.addSink(&lr);
         lr.addSink(&writer);
         ret = writer.runChain(cc);

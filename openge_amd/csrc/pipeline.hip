@@ -362,6 +362,22 @@ extern "C" int oge_bam_coverage_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t z
     return rc;
 }
 
+extern "C" int oge_bam_targets_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const oge_targets_opts *opts, oge_targets_result *result,
+                                   const oge_target **d_targets, const uint8_t **d_text) {
+    if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
+    if (!opts || !result || !d_targets || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
+    OgeCall call(ctx, /*hold=*/true);
+    *d_targets = nullptr;
+    if (d_text) *d_text = nullptr;
+    uint8_t *X;
+    uint64_t *xoff, n;
+    BamFile f;
+    const int rc = decode_for_qc(ctx, d_z, zbytes, &X, &xoff, &n, &f);
+    if (rc) return rc;
+    return oge_targets_impl(ctx, X, xoff, n, (int32_t)f.ref_lens.size(), f.ref_lens.data(), ctx->ref_names.data(), ctx->ref_names.size(), opts,
+                            result, d_targets, d_text);
+}
+
 extern "C" int oge_bam_count_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint64_t *n_reads) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!n_reads || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");

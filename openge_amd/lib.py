@@ -92,6 +92,27 @@ def decode_compare_diff(image: bytes) -> list[tuple]:
         out.append((side, refid, pos, surplus, struct.unpack_from(f"<{nops}I", image, p + 24)))
         p += 24 + 4 * nops
     return out
+
+
+class TargetsOpts(C.Structure):
+    """Mirror of oge_targets_opts (include/openge_hip.h)."""
+    _fields_ = [("max_interval", C.c_int32), ("gap", C.c_int32), ("want", C.c_uint32)]
+
+
+class TargetsResult(C.Structure):
+    """Mirror of oge_targets_result."""
+    FIELDS = ("reads_used", "events", "intervals", "dropped_long", "targets", "text_bytes")
+    _fields_ = [(k, C.c_uint64) for k in FIELDS]
+
+
+TARGETS_TEXT = 1
+
+
+def _ref_table(refs) -> tuple[np.ndarray, bytes]:
+    """[(name, length)] -> (lengths i32, the names NUL-terminated one after the other)"""
+    return np.array([ln for _, ln in refs], np.int32), b"".join(nm.encode() + b"\0" for nm, _ in refs)
+
+
 TEXT_SAM, TEXT_FASTQ = 0, 1
 
 
@@ -356,6 +377,10 @@ def lib() -> C.CDLL:
         "oge_coverage_layout": (C.c_int, [i32, vp, i32, vp]),
         "oge_coverage_dev": (C.c_int, [vp, vp, vp, u64, i32, vp, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(i32)]),
         "oge_coverage": (C.c_int, [vp, vp, u64, vp, u64, i32, vp, i32, vp, u64, C.POINTER(u64), C.POINTER(i32)]),
+        "oge_targets_opts_init": (None, [vp]),
+        "oge_targets_dev": (C.c_int, [vp, vp, vp, u64, i32, vp, C.c_char_p, u64, vp, vp, C.POINTER(vp), C.POINTER(vp)]),
+        "oge_targets": (C.c_int, [vp, vp, u64, vp, u64, i32, vp, C.c_char_p, u64, vp, vp, vp, u64, vp, u64]),
+        "oge_bam_targets_dev": (C.c_int, [vp, vp, u64, vp, vp, C.POINTER(vp), C.POINTER(vp)]),
         "oge_bam_stats_dev": (C.c_int, [vp, vp, u64, u32, vp, C.POINTER(vp), C.POINTER(vp)]),
         "oge_bam_coverage_dev": (C.c_int, [vp, vp, u64, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]),
         "oge_bam_count_dev": (C.c_int, [vp, vp, u64, C.POINTER(u64)]),
@@ -786,6 +811,53 @@ class Context:
         if diff:
             out["diff"] = decode_compare_diff(buf[:nb.value].tobytes())
         return out
+
+    # ---- realignment targets (csrc/targets.hip)
+    @staticmethod
+    def _targets_opts(max_interval: int, gap: int) -> TargetsOpts:
+        o = TargetsOpts()
+        lib().oge_targets_opts_init(C.byref(o))
+        o.max_interval, o.gap, o.want = max_interval, gap, TARGETS_TEXT
+        return o
+
+    def _targets_out(self, res: TargetsResult, dt, dx) -> tuple[dict, np.ndarray, bytes]:
+        raw = np.frombuffer(self._fetch(dt.value or 0, 16 * res.targets), np.int32).reshape(res.targets, 4).astype(np.int64)
+        raw[:, 3] &= 0xFFFFFFFF  # n_events is unsigned
+        return {k: getattr(res, k) for k in TargetsResult.FIELDS}, raw, self._fetch(dx.value or 0, res.text_bytes)
+
+    def targets_dev(self, d_recs, d_off, n: int, refs, max_interval: int = 500, gap: int = 0) -> tuple[dict, np.ndarray, bytes]:
+        """oge_targets_dev on device records; refs = [(name, length)] -> (the counters of oge_targets_result, the
+        intervals as int64 (targets, 4): refID, start, stop, n_events, the text "contig:start-stop\\n" per interval)."""
+        lens, names = _ref_table(refs)
+        o, res, dt, dx = self._targets_opts(max_interval, gap), TargetsResult(), C.c_void_p(), C.c_void_p()
+        check(lib().oge_targets_dev(self.h, d_recs, d_off, n, len(lens), _ptr(lens) if len(lens) else None, names, len(names),
+                                    C.byref(o), C.byref(res), C.byref(dt), C.byref(dx)), self.h)
+        return self._targets_out(res, dt, dx)
+
+    def targets(self, recs: np.ndarray, offs: np.ndarray, n: int, refs, max_interval: int = 500, gap: int = 0) -> tuple[dict, np.ndarray, bytes]:
+        """oge_targets: the same from host buffers (a sizing call, then the call that copies the outputs)."""
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens, names = _ref_table(refs)
+        o, res = self._targets_opts(max_interval, gap), TargetsResult()
+        args = (self.h, _ptr(recs), max(recs.nbytes - 16, 0), _ptr(offs), n, len(lens), _ptr(lens) if len(lens) else None, names,
+                len(names), C.byref(o), C.byref(res))
+        rc = lib().oge_targets(*args, None, 0, None, 0)
+        if not (rc == -3 and res.targets):  # OGE_ERR_LIMIT with the sizes: the sizing call
+            check(rc, self.h)
+        arr, text = np.zeros((max(res.targets, 1), 4), np.int32), np.zeros(max(res.text_bytes, 1), np.uint8)
+        if rc:
+            check(lib().oge_targets(*args, _ptr(arr), res.targets, _ptr(text), res.text_bytes), self.h)
+        out = arr[:res.targets].astype(np.int64)
+        out[:, 3] &= 0xFFFFFFFF
+        return {k: getattr(res, k) for k in TargetsResult.FIELDS}, out, text[:res.text_bytes].tobytes()
+
+    def bam_targets(self, data: bytes, max_interval: int = 500, gap: int = 0) -> tuple[dict, np.ndarray, bytes]:
+        """`openge targets` of a whole BAM file (oge_bam_targets_dev on a copy of the file in HBM)."""
+        def run(dz, nbytes):
+            o, res, dt, dx = self._targets_opts(max_interval, gap), TargetsResult(), C.c_void_p(), C.c_void_p()
+            check(lib().oge_bam_targets_dev(self.h, dz, nbytes, C.byref(o), C.byref(res), C.byref(dt), C.byref(dx)), self.h)
+            return self._targets_out(res, dt, dx)
+        return self._with_file(data, run)
 
     # ---- SAM / FASTQ text (csrc/sam.hip)
     def text_size_dev(self, d_recs, d_off, n: int, opts: TextOpts, d_text_off, d_host_mark) -> tuple[int, int]:
