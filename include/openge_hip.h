@@ -717,6 +717,69 @@ int oge_targets(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const uin
 int oge_bam_targets_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const oge_targets_opts *opts,
                         oge_targets_result *result, const oge_target **d_targets, const uint8_t **d_text);
 
+/* ---- duplication metrics of marked records (dedup --metrics, mergesort -M --metrics, openge dupmetrics) ----
+ * Picard MarkDuplicates' metrics file for records that already carry their final FLAG (the reference writes none,
+ * algorithms/mark_duplicates.cpp); DESIGN.md section 26, the model is tests/dupmetrics_model.py.  The counts are
+ * a pure function of the marked records: each contributes its FLAG, its refID and the library of its RG tag.
+ * Library of a record: the RG value as the dedup's input pass finds it (FindTag semantics: the tags walked from
+ *   the end of QUAL; the first tag named RG, of whatever type byte, gives the bytes up to the next NUL or the
+ *   record's end; the walk ends without one at a type byte of 0, an unknown type, a B array whose header does not
+ *   fit, whose subtype is unknown or whose count is negative, and when the next tag would start at or past the
+ *   record's end or with a NUL; a block_size outside [32, 10000] has no tags to walk).  A non-empty value found in
+ *   rg_ids of oge_markdup_opts gives rg_lib[g] (the first such g); no tag, an empty or an unlisted value gives
+ *   unknown_lib.  EVERY record is resolved, unmapped and secondary ones too.
+ * Class of a record, the first rule that applies (buildSortedReadEndLists, :202-209): FLAG 0x4 set or refID == -1:
+ *   unmapped; 0x100 set: secondary; 0x1 set and 0x8 clear: pair; otherwise unpaired.  0x800 has no meaning of its own.
+ * Counters, all counts of READS, so that the counts of any partition of a record set add up: the four classes, and
+ *   unpaired_dups / pair_read_dups = the records of class unpaired / pair whose FLAG has 0x400 (a secondary or
+ *   unmapped record with 0x400 counts only under its class).
+ * Derived (oge_dup_metrics_text): READ_PAIRS_EXAMINED = pair_reads_examined / 2 and READ_PAIR_DUPLICATES =
+ *   pair_read_dups / 2, both floored; READ_PAIR_OPTICAL_DUPLICATES = 0; PERCENT_DUPLICATION = (unpaired_dups +
+ *   pair_read_dups) / (unpaired_examined + pair_reads_examined), 0 when the denominator is 0;
+ *   ESTIMATED_LIBRARY_SIZE by oge_estimate_library_size(READ_PAIRS_EXAMINED, READ_PAIRS_EXAMINED -
+ *   READ_PAIR_DUPLICATES); the ROI histogram at x = 1..100 is L * (1 - exp(-(x * n) / L)) / c in double (L the
+ *   estimate, n the pairs, c the unique pairs), written only when the file has exactly one row and that row has an
+ *   estimate above 0 (with no unique pair the bisection runs on NaNs and leaves 0).
+ * Counters (oge_ctx_counter): "dupmetrics_tile_records" = the records one workgroup takes per tile,
+ * "dupmetrics_lds_libs" = the libraries whose counts a workgroup sums in LDS (more: the per-wave sums go straight
+ * to the table in HBM).  Stage name for oge_ctx_timing: "dup_metrics".
+ * The counters' struct has no typedef: its tag is also the name of the host-buffer entry point. */
+struct oge_dup_metrics {
+    uint64_t unpaired_examined, pair_reads_examined, secondary, unmapped, unpaired_dups, pair_read_dups;
+};
+/* Records d_recs + d_off[i] (n offsets; the arena carries 16 bytes of slack behind the last record).  Of opts only
+ * the read-group table is read (rg_ids, rg_ids_bytes, rg_lib, n_rg, unknown_lib).  out[n_lib], indexed by library
+ * id, is SET (callers sum over ranges and ranks); n_lib = 1 + the largest of rg_lib[] and unknown_lib.  Synchronous
+ * on the context's stream.  OGE_ERR_ARG: a library id outside [0, n_lib), n_lib outside [1, 32768]. */
+int oge_dup_metrics_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_markdup_opts *opts,
+                        int32_t n_lib, struct oge_dup_metrics *out);
+/* Host-buffer form: uploads the records and offsets, then the same. */
+int oge_dup_metrics(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const uint64_t *rec_off, uint64_t n,
+                    const oge_markdup_opts *opts, int32_t n_lib, struct oge_dup_metrics *out);
+/* A whole BAM file resident in HBM (4-byte aligned): framing index, inflate, header, record walk, then the counts
+ * against the read-group table of the file's own header, numbered as oge_bam_markdup_opts numbers it.  *out
+ * (*n_lib entries, by library id) and *lib_names (the *n_lib names NUL-terminated one after the other, names_bytes
+ * in all; "" for an id that no @RG names) are host memory of the context, valid until its next call of this
+ * function.  *unknown_lib = the id of "Unknown Library": that of the @RG lines without an LB, or an id of its own,
+ * then without a name, when every @RG has one. */
+int oge_bam_dup_metrics_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const struct oge_dup_metrics **out, int32_t *n_lib,
+                            const char **lib_names, uint64_t *names_bytes, int32_t *unknown_lib);
+/* Picard's estimateLibrarySize, host only, all in double in this order of operations: n = pairs, c = unique_pairs,
+ * f(x) = c / x - 1 + exp(-n / x); no estimate (returns 1, *size untouched) unless n > 0 and n - c > 0; m = 1,
+ * M = 100; while f(M * c) > 0: M *= 10; 40 bisection steps on r = (m + M) / 2 with u = f(r * c): stop at u == 0,
+ * m = r when u > 0, else M = r; *size = (uint64)(c * (m + M) / 2), returns 0. */
+int oge_estimate_library_size(uint64_t pairs, uint64_t unique_pairs, uint64_t *size);
+/* The metrics file, host only.  n_rows rows: names[i] (NUL-terminated) with the counters m[i], written sorted by
+ * name in byte order; command_line goes behind "# " on the second line.
+ *   ## htsjdk.samtools.metrics.StringHeader / # <command line> / <blank> /
+ *   ## METRICS CLASS<TAB>picard.sam.DuplicationMetrics / the ten column names / one row per library / <blank> /
+ *   [## HISTOGRAM<TAB>java.lang.Double / BIN<TAB>VALUE / 100 lines "x.0<TAB>%.6f" / <blank>]
+ * Integers in decimal, PERCENT_DUPLICATION as %.6f, the library size empty when there is no estimate.
+ * *len_out = the bytes of the whole text; buf (cap bytes, may be NULL with cap 0) gets min(cap - 1, *len_out)
+ * of them and a NUL, as oge_bam_header_text does. */
+int oge_dup_metrics_text(const char *const *names, const struct oge_dup_metrics *m, int32_t n_rows, const char *command_line, char *buf,
+                         uint64_t cap, uint64_t *len_out);
+
 /* ---- SAM and FASTQ text of records in HBM (openge view, -F sam|fastq) ----------------------------------
  * The reference's SamWriter::write (util/sam_writer.cpp:90-217) and the single-stream form of
  * FastqWriter::write (util/fastq_writer.cpp:99-100) on the device; DESIGN.md section 21.

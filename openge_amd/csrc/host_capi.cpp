@@ -7,6 +7,8 @@
 #include <algorithm>
 #include <atomic>
 #include <climits>
+#include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -185,6 +187,80 @@ int oge_bam_write(const char *path, const char *header_text, uint64_t header_len
 }
 
 } // extern "C"
+
+// ----------------------------------------------------------------------------- duplication metrics (host side)
+// Picard's DuplicationMetrics.estimateLibrarySize; the order of the operations is part of the definition
+// (include/openge_hip.h, tests/dupmetrics_model.py): the tests ask for the same doubles.
+extern "C" int oge_estimate_library_size(uint64_t pairs, uint64_t unique_pairs, uint64_t *size) {
+    if (!(pairs > 0 && pairs > unique_pairs)) return 1;
+    const double n = (double)pairs, c = (double)unique_pairs;
+    auto f = [&](double x) { return c / x - 1 + exp(-n / x); };
+    double m = 1, M = 100;
+    while (f(M * c) > 0) M *= 10;
+    for (int i = 0; i < 40; ++i) {
+        const double r = (m + M) / 2;
+        const double u = f(r * c);
+        if (u == 0) break;
+        if (u > 0) m = r;
+        else M = r;
+    }
+    if (size) *size = (uint64_t)(c * (m + M) / 2);
+    return 0;
+}
+
+extern "C" int oge_dup_metrics_text(const char *const *names, const struct oge_dup_metrics *m, int32_t n_rows, const char *command_line, char *buf,
+                                    uint64_t cap, uint64_t *len_out) {
+    if (n_rows < 0 || (n_rows && (!names || !m)) || !command_line) return oge_fail(nullptr, OGE_ERR_ARG, "oge_dup_metrics_text: null argument");
+    std::vector<int32_t> order(n_rows);
+    for (int32_t i = 0; i < n_rows; ++i) {
+        if (!names[i]) return oge_fail(nullptr, OGE_ERR_ARG, "oge_dup_metrics_text: null name");
+        order[i] = i;
+    }
+    // byte order (strcmp compares unsigned chars), whatever the locale says; equal names keep the caller's order
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return strcmp(names[a], names[b]) < 0; });
+    std::string t = "## htsjdk.samtools.metrics.StringHeader\n# ";
+    t += command_line;
+    t += "\n\n## METRICS CLASS\tpicard.sam.DuplicationMetrics\n"
+         "LIBRARY\tUNPAIRED_READS_EXAMINED\tREAD_PAIRS_EXAMINED\tSECONDARY_OR_SUPPLEMENTARY_RDS\tUNMAPPED_READS\tUNPAIRED_READ_DUPLICATES\t"
+         "READ_PAIR_DUPLICATES\tREAD_PAIR_OPTICAL_DUPLICATES\tPERCENT_DUPLICATION\tESTIMATED_LIBRARY_SIZE\n";
+    char num[64];
+    uint64_t pairs = 0, dup_pairs = 0, size = 0;
+    bool has_size = false;
+    for (int32_t i : order) {
+        const struct oge_dup_metrics &x = m[i];
+        pairs = x.pair_reads_examined / 2;
+        dup_pairs = x.pair_read_dups / 2;
+        const uint64_t den = x.unpaired_examined + x.pair_reads_examined;
+        const double pct = den ? (double)(x.unpaired_dups + x.pair_read_dups) / (double)den : 0.0;
+        has_size = oge_estimate_library_size(pairs, pairs - dup_pairs, &size) == 0;  // more duplicates than pairs: none
+        t += names[i];
+        for (uint64_t v : {x.unpaired_examined, pairs, x.secondary, x.unmapped, x.unpaired_dups, dup_pairs, (uint64_t)0}) t += "\t" + std::to_string(v);
+        snprintf(num, sizeof num, "\t%.6f\t", pct);
+        t += num;
+        if (has_size) t += std::to_string(size);
+        t += "\n";
+    }
+    t += "\n";
+    // the return on investment of sequencing x times as deep; an estimate of 0 (no unique pair: the bisection ran on
+    // NaNs) has none
+    if (n_rows == 1 && has_size && size) {
+        const double L = (double)size, n = (double)pairs, c = (double)(pairs - dup_pairs);
+        t += "## HISTOGRAM\tjava.lang.Double\nBIN\tVALUE\n";
+        for (int k = 1; k <= 100; ++k) {
+            const double x = (double)k;
+            snprintf(num, sizeof num, "%d.0\t%.6f\n", k, L * (1 - exp(-(x * n) / L)) / c);
+            t += num;
+        }
+        t += "\n";
+    }
+    if (len_out) *len_out = t.size();
+    if (buf && cap) {
+        const size_t k = std::min<size_t>(cap - 1, t.size());
+        memcpy(buf, t.data(), k);
+        buf[k] = 0;
+    }
+    return OGE_OK;
+}
 
 // ----------------------------------------------------------------------------- Filter (mergesort -r/-q)
 extern "C" void oge_filter_opts_init(oge_filter_opts *o) {  // Filter::Filter (filter.cpp:185-194)

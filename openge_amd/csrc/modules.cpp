@@ -31,6 +31,16 @@ using TimePoint = std::chrono::steady_clock::time_point;
 static TimePoint clk() { return std::chrono::steady_clock::now(); }
 static double sec(TimePoint a, TimePoint z) { return std::chrono::duration<double>(z - a).count(); }
 
+// counts of reads: the counts of two parts of a record set add up
+static void add_metrics(OgeDupMetrics &a, const OgeDupMetrics &b) {
+    a.unpaired_examined += b.unpaired_examined;
+    a.pair_reads_examined += b.pair_reads_examined;
+    a.secondary += b.secondary;
+    a.unmapped += b.unmapped;
+    a.unpaired_dups += b.unpaired_dups;
+    a.pair_read_dups += b.pair_read_dups;
+}
+
 int ChainContext::fail(const std::string &where) {
     fprintf(stderr, "openge: %s: %s\n", where.c_str(), oge_last_error(ctx));
     return -1;
@@ -133,7 +143,8 @@ void ChainContext::close_ranks() {
 // Cut the batch into G contiguous input ranges and run oge_sort_markdup_dist on every rank (one host
 // thread each).  A rank whose own preparation failed still joins the collectives with an empty shard
 // so the others finish, and the failure is reported.
-int run_ranks(ChainContext &cc, ReadBatch &b, bool sort, const oge_markdup_opts *opts, uint64_t *n_dup) {
+int run_ranks(ChainContext &cc, ReadBatch &b, bool sort, const oge_markdup_opts *opts, uint64_t *n_dup, std::vector<OgeDupMetrics> *metrics,
+              double *metrics_ms) {
     const bool sharded = !b.shards.empty();  // the reader left every rank its own input shard
     if (cc.init_ranks() || (!sharded && cc.to_device(b))) return -1;
     const int G = cc.gpus;
@@ -148,6 +159,17 @@ int run_ranks(ChainContext &cc, ReadBatch &b, bool sort, const oge_markdup_opts 
     std::vector<int> rcs(G, 0);
     std::vector<uint64_t> nds(G, 0);
     std::vector<std::string> why(G);
+    // --metrics: every rank counts the slice it was left with, on its own device
+    const bool count = metrics && opts;
+    std::vector<std::vector<OgeDupMetrics>> part(G, std::vector<OgeDupMetrics>(count ? metrics->size() : 0));
+    std::vector<double> part_ms(G, 0);
+    auto count_slice = [&](int g) {
+        if (!count || rcs[g]) return;
+        oge_ctx *c = cc.rank_ctx[g];
+        rcs[g] = oge_dup_metrics_dev(c, sl[g].d_recs, sl[g].d_offs, sl[g].n, opts, (int32_t)part[g].size(), part[g].data());
+        if (rcs[g]) why[g] = oge_last_error(c);
+        else oge_ctx_timing(c, "dup_metrics", &part_ms[g]);
+    };
     std::vector<std::thread> ts;
     for (int g = 0; g < G; ++g)
         ts.emplace_back([&, g]() {
@@ -160,6 +182,7 @@ int run_ranks(ChainContext &cc, ReadBatch &b, bool sort, const oge_markdup_opts 
                 if (rcs[g]) why[g] = oge_last_error(c);
                 sl[g] = {c, dout, doff, no};
                 nds[g] = nd;
+                count_slice(g);
                 return;
             }
             const uint64_t lo = cut[g], m = cut[g + 1] - lo, bytes = boff[g + 1] - boff[g];
@@ -177,6 +200,7 @@ int run_ranks(ChainContext &cc, ReadBatch &b, bool sort, const oge_markdup_opts 
             rcs[g] = rc ? rc : rd;
             sl[g] = {c, dout, doff, no};
             nds[g] = nd;
+            count_slice(g);
         });
     for (auto &t : ts) t.join();
     for (int g = 0; g < G; ++g)
@@ -184,6 +208,11 @@ int run_ranks(ChainContext &cc, ReadBatch &b, bool sort, const oge_markdup_opts 
             fprintf(stderr, "openge: rank %d: %s\n", g, why[g].c_str());
             return -1;
         }
+    if (count) {
+        for (int g = 0; g < G; ++g)
+            for (size_t k = 0; k < metrics->size(); ++k) add_metrics((*metrics)[k], part[g][k]);
+        if (metrics_ms) *metrics_ms += *std::max_element(part_ms.begin(), part_ms.end());
+    }
     cc.free_device(b);
     b.shards.clear();
     b.slices = sl;
@@ -220,6 +249,11 @@ int AlgorithmModule::runChain(ChainContext &cc) {
             marked = true;
     }
     cc.free_device(b);
+    // --metrics: every part of the marked output has been counted by now (the chunked sort's ranges only when
+    // the writer asked for them)
+    for (AlgorithmModule *m = head; m; m = m->sink_)
+        if (auto *md = dynamic_cast<MarkDuplicates *>(m))
+            if (!md->metricsFilename.empty() && md->writeMetrics()) return -1;
     return 0;
 }
 
@@ -973,11 +1007,16 @@ struct MdOpts {
     oge_markdup_opts o;
     std::string ids;
     std::vector<int16_t> libs;
+    std::vector<std::string> lib_names;  // by library id: "" where no @RG names the id (0, and an unknown_lib of its own)
 };
+static void markdup_opts(const BamHeaderModel &header, int32_t n_ref, bool compat, int split, MdOpts &m);
 static void markdup_opts(const ReadBatch &b, bool compat, int split, MdOpts &m) {
+    markdup_opts(b.header, (int32_t)b.ref_names.size(), compat, split, m);
+}
+static void markdup_opts(const BamHeaderModel &header, int32_t n_ref, bool compat, int split, MdOpts &m) {
     std::map<std::string, int16_t> lib_ids;
     int16_t next = 1;
-    for (auto &rg : b.header.rg) {
+    for (auto &rg : header.rg) {
         std::string lib = rg.lb.empty() ? std::string("Unknown Library") : rg.lb;
         auto it = lib_ids.find(lib);
         if (it == lib_ids.end()) it = lib_ids.emplace(lib, next++).first;
@@ -988,14 +1027,71 @@ static void markdup_opts(const ReadBatch &b, bool compat, int split, MdOpts &m) 
     auto unk = lib_ids.find("Unknown Library");
     m.libs.push_back(0);
     memset(&m.o, 0, sizeof m.o);
-    m.o.n_ref = (int32_t)b.ref_names.size();
+    m.o.n_ref = n_ref;
     m.o.rg_ids = m.ids.c_str();
     m.o.rg_ids_bytes = m.ids.size();
     m.o.rg_lib = m.libs.data();
-    m.o.n_rg = (int32_t)b.header.rg.size();
+    m.o.n_rg = (int32_t)header.rg.size();
     m.o.unknown_lib = unk != lib_ids.end() ? unk->second : next;
     m.o.compat_nonverbose_index = compat ? 1 : 0;
     m.o.split_chains = split;
+    m.lib_names.assign((size_t)std::max<int16_t>(m.o.unknown_lib, (int16_t)(next - 1)) + 1, std::string());
+    for (auto &kv : lib_ids) m.lib_names[kv.second] = kv.first;
+}
+
+// MarkDuplicates::metricsFilename: the module's counters sized and named for this header's libraries (once per
+// chain), and the counts of one more part of the marked output added to them
+static void metrics_begin(MarkDuplicates *md, const MdOpts &m) {
+    md->metricsLibraries = m.lib_names;
+    md->metricsUnknown = m.o.unknown_lib;
+    md->metrics.assign(m.lib_names.size(), OgeDupMetrics{});
+    md->metricsMs = 0;
+}
+static int metrics_count(MarkDuplicates *md, oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_offs, uint64_t n, const MdOpts &m) {
+    std::vector<OgeDupMetrics> part(md->metrics.size());
+    if (oge_dup_metrics_dev(ctx, d_recs, d_offs, n, &m.o, (int32_t)part.size(), part.data())) return -1;
+    for (size_t k = 0; k < part.size(); ++k) add_metrics(md->metrics[k], part[k]);
+    double ms = 0;
+    if (!oge_ctx_timing(ctx, "dup_metrics", &ms) && ms > 0) md->metricsMs += ms;
+    return 0;
+}
+
+// One row for every library an @RG names, one more "Unknown Library" row when none does and a record resolved to it
+// (names by library id, "" = not named); oge_dup_metrics_text sorts them.
+static int metrics_text(const std::vector<std::string> &names, int unknown, const std::vector<OgeDupMetrics> &m, const std::string &command_line,
+                        std::string &text) {
+    std::vector<const char *> row_names;
+    std::vector<OgeDupMetrics> rows;
+    for (size_t k = 0; k < names.size() && k < m.size(); ++k)
+        if (!names[k].empty()) row_names.push_back(names[k].c_str()), rows.push_back(m[k]);
+    if (unknown >= 0 && (size_t)unknown < m.size() && names[unknown].empty()) {
+        const OgeDupMetrics &u = m[unknown];
+        if (u.unpaired_examined | u.pair_reads_examined | u.secondary | u.unmapped | u.unpaired_dups | u.pair_read_dups)
+            row_names.push_back("Unknown Library"), rows.push_back(u);
+    }
+    std::string cl = command_line;
+    while (!cl.empty() && cl.back() == ' ') cl.pop_back();
+    uint64_t need = 0;
+    if (oge_dup_metrics_text(row_names.data(), rows.data(), (int32_t)rows.size(), cl.c_str(), nullptr, 0, &need)) return -1;
+    text.resize(need + 1);
+    if (oge_dup_metrics_text(row_names.data(), rows.data(), (int32_t)rows.size(), cl.c_str(), &text[0], need + 1, &need)) return -1;
+    text.resize(need);
+    return 0;
+}
+
+static int write_text_file(const std::string &out, const std::vector<uint8_t> &text);
+
+int MarkDuplicates::writeMetrics() const {
+    std::string text;
+    if (metrics_text(metricsLibraries, metricsUnknown, metrics, metricsCommandLine, text)) {
+        fprintf(stderr, "openge: MarkDuplicates: metrics: %s\n", oge_last_error(nullptr));
+        return -1;
+    }
+    if (write_text_file(metricsFilename, std::vector<uint8_t>(text.begin(), text.end()))) return -1;
+    if (verbose_) fprintf(stderr, "[openge] MarkDuplicates: metrics of %zu libraries to %s, stage dup_metrics %.3f ms\n",
+                          (size_t)std::count_if(metricsLibraries.begin(), metricsLibraries.end(), [](const std::string &s) { return !s.empty(); }),
+                          metricsFilename.c_str(), metricsMs);
+    return 0;
 }
 
 // ----------------------------------------------------------------------------------- Filter
@@ -1137,9 +1233,11 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
     if (cc.gpus > 1 && order_ == BamHeaderModel::COORDINATE) {  // --gpus G: range-split sort (+ dedup) over G ranks
         MdOpts m;
         if (md) markdup_opts(b, md->compatNonverbose, md->splitChains, m);
+        const bool count = md && !md->metricsFilename.empty();
+        if (count) metrics_begin(md, m);
         uint64_t nd = 0;
         const auto t0 = clk();
-        if (run_ranks(cc, b, true, md ? &m.o : nullptr, &nd)) return -1;
+        if (run_ranks(cc, b, true, md ? &m.o : nullptr, &nd, count ? &md->metrics : nullptr, count ? &md->metricsMs : nullptr)) return -1;
         if (md) md->duplicates = nd;
         b.header.sort_order = order_;
         if (verbose_)
@@ -1161,10 +1259,17 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
         const uint64_t chunk = ce ? strtoull(ce, nullptr, 10) : 0, n = b.n;
         const int32_t n_ref = (int32_t)b.ref_names.size();
         b.produce = [arena, mo, md, chunk, n, n_ref](ChainContext &c, const ReadBatch::RangeSink &sink) -> int {
+            // --metrics: every marked range is counted in front of the sink (which may drop its duplicates)
+            const bool count = md && !md->metricsFilename.empty();
+            if (count) metrics_begin(md, *mo);
+            const ReadBatch::RangeSink counted = [&](const uint8_t *r, const uint64_t *o, uint64_t m) -> int {
+                if (metrics_count(md, c.ctx, r, o, m, *mo)) return c.fail("MarkDuplicates: metrics");
+                return sink(r, o, m);
+            };
             struct Tramp {
                 const ReadBatch::RangeSink *s;
                 static int call(void *u, const uint8_t *r, const uint64_t *o, uint64_t m) { return (*((Tramp *)u)->s)(r, o, m); }
-            } tr{&sink};
+            } tr{count ? &counted : &sink};
             uint64_t nd = 0, runs = 0, ranges = 0;
             const int rc = oge_sort_markdup_chunked(c.ctx, arena->recs.data(), arena->offs.data(), n, n_ref, md ? &mo->o : nullptr,
                                                     chunk, &Tramp::call, &tr, &nd, &runs, &ranges);
@@ -1190,11 +1295,11 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
     if (verbose_) oge_ctx_sync(cc.ctx);
     const auto t1a = clk();
     int rc;
+    MdOpts m;
     if (order_ == BamHeaderModel::QUERYNAME) {  // -b; a MarkDuplicates sink then runs on its own
         rc = oge_sort_name_dev(cc.ctx, b.d_recs, b.d_offs, b.n, perm);
         if (!rc) rc = oge_gather_records_dev(cc.ctx, b.d_recs, b.d_offs, perm, b.n, out, out_off);
     } else if (md) {  // mergesort -M: one fused device pipeline (sort, dedup, gather with 0x400 applied)
-        MdOpts m;
         markdup_opts(b, md->compatNonverbose, md->splitChains, m);
         uint64_t nd = 0;
         rc = oge_sort_markdup_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &m.o, perm, out, out_off, &nd);
@@ -1216,6 +1321,10 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
         fprintf(stderr, "[openge] ReadSorter stages (ms):%s\n", st.c_str());
     }
     if (rc) return cc.fail("ReadSorter");
+    if (md && order_ == BamHeaderModel::COORDINATE && !md->metricsFilename.empty()) {  // --metrics: the marked output, before any removal
+        metrics_begin(md, m);
+        if (metrics_count(md, cc.ctx, out, out_off, b.n, m)) return cc.fail("MarkDuplicates: metrics");
+    }
     cc.free_device(b);
     b.d_recs = (uint8_t *)out_buf.release();
     b.d_offs = (uint64_t *)off_buf.release();
@@ -1234,8 +1343,10 @@ int MarkDuplicates::runInternal(ChainContext &cc, ReadBatch &b) {
         }
         MdOpts m;
         markdup_opts(b, false, splitChains, m);
+        const bool count = !metricsFilename.empty();
+        if (count) metrics_begin(this, m);
         uint64_t nd = 0;
-        if (run_ranks(cc, b, false, &m.o, &nd)) return -1;
+        if (run_ranks(cc, b, false, &m.o, &nd, count ? &metrics : nullptr, count ? &metricsMs : nullptr)) return -1;
         duplicates = nd;
         b.drop_duplicates = removeDuplicates;
         return 0;
@@ -1248,6 +1359,10 @@ int MarkDuplicates::runInternal(ChainContext &cc, ReadBatch &b) {
     uint64_t nd = 0;
     if (oge_markdup_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &m.o, dup.as<uint8_t>(), 1, &nd) || oge_ctx_sync(cc.ctx)) return cc.fail("MarkDuplicates");
     duplicates = nd;
+    if (!metricsFilename.empty()) {  // the records carry their final FLAG now; -r drops them in the writer
+        metrics_begin(this, m);
+        if (metrics_count(this, cc.ctx, b.d_recs, b.d_offs, b.n, m)) return cc.fail("MarkDuplicates: metrics");
+    }
     b.host_valid = false;
     b.drop_duplicates = removeDuplicates;
     return 0;
@@ -2010,6 +2125,31 @@ struct QcInput {
         return oge_targets_dev(cc.ctx, b.d_recs, b.d_offs, b.n, (int32_t)sam_lens.size(), sam_lens.data(), sam_names.data(), sam_names.size(), o,
                                res, d_targets, d_text);
     }
+    // the counters by library id, the ids' names ("" = no @RG names it) and the id of "Unknown Library"
+    int dup_metrics(std::vector<OgeDupMetrics> &m, std::vector<std::string> &names, int *unknown) {
+        if (sam) {
+            MdOpts mo;
+            markdup_opts(b, false, 0, mo);
+            names = mo.lib_names;
+            *unknown = mo.o.unknown_lib;
+            m.assign(names.size(), OgeDupMetrics{});
+            return oge_dup_metrics_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &mo.o, (int32_t)m.size(), m.data());
+        }
+        const OgeDupMetrics *out = nullptr;
+        const char *nm = nullptr;
+        int32_t n_lib = 0, unk = 0;
+        uint64_t names_bytes = 0;
+        const int rc = oge_bam_dup_metrics_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, &out, &n_lib, &nm, &names_bytes, &unk);
+        if (rc) return rc;
+        m.assign(out, out + n_lib);
+        names.clear();
+        for (int32_t k = 0; k < n_lib; ++k) {
+            names.emplace_back(nm);
+            nm += names.back().size() + 1;
+        }
+        *unknown = unk;
+        return 0;
+    }
     int coverage(int32_t binsize, const uint32_t **d_bins, uint64_t *nb, uint64_t *skipped, int32_t *overflow, int32_t *n_ref, const char **names,
                  const int32_t **lens) {
         if (!sam) {
@@ -2192,6 +2332,34 @@ int targets_bam_file(ChainContext &cc, const std::string &path, const std::strin
     }
     if (cc.verbose) report_targets(res, max_interval, gap);
     report_stages(cc, "targets", sec(t0, clk()));
+    return 0;
+}
+
+int dupmetrics_bam_file(ChainContext &cc, const std::string &path, const std::string &out, const std::string &command_line) {
+    QcInput in(cc);
+    if (in.load(path)) return -1;
+    std::vector<OgeDupMetrics> m;
+    std::vector<std::string> names;
+    int unknown = 0;
+    const int rc = in.dup_metrics(m, names, &unknown);
+    in.z.buf.reset();
+    if (rc) return cc.fail("dupmetrics");
+    const auto t0 = clk();
+    std::string text;
+    if (metrics_text(names, unknown, m, command_line, text)) {
+        fprintf(stderr, "openge: dupmetrics: %s\n", oge_last_error(nullptr));
+        return -1;
+    }
+    if (out == "stdout" || out == "-") {
+        const bool ok = fwrite(text.data(), 1, text.size(), stdout) == text.size() && fflush(stdout) == 0 && !ferror(stdout);
+        if (!ok) {
+            fprintf(stderr, "openge: error writing to stdout\n");
+            return -1;
+        }
+    } else if (write_text_file(out, std::vector<uint8_t>(text.begin(), text.end()))) {
+        return -1;
+    }
+    report_stages(cc, "dup_metrics", sec(t0, clk()));
     return 0;
 }
 

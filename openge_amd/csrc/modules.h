@@ -20,6 +20,9 @@
 
 namespace oge {
 
+// the struct by a name of its own: the plain name is the host-buffer entry point's
+using OgeDupMetrics = struct ::oge_dup_metrics;
+
 struct ChainContext;
 
 // Records of one chain, resident in host memory, HBM, or both.
@@ -219,6 +222,16 @@ public:
     bool compatNonverbose = false;  // reproduce the index bug of runs without -v
     int splitChains = 0;            // > 1 = the result of the split-by-chromosome chains
     uint64_t duplicates = 0;
+    // --metrics FILE: Picard's duplication metrics of the marked records (oge_dup_metrics_dev), counted before any
+    // removal wherever the marking ran -- in place, fused with the sort, per range of the chunked sort, per rank --
+    // and summed here by library id; runChain writes the file (oge_dup_metrics_text) once the chain has run.
+    // metricsCommandLine goes into the file's header.
+    std::string metricsFilename, metricsCommandLine;
+    std::vector<OgeDupMetrics> metrics;       // by library id
+    std::vector<std::string> metricsLibraries;  // the ids' names, "" where no @RG names the id
+    int metricsUnknown = 0;                     // the id of "Unknown Library"
+    double metricsMs = 0;                       // stage dup_metrics, summed over the calls (ranks: the slowest)
+    int writeMetrics() const;
 protected:
     int runInternal(ChainContext &cc, ReadBatch &b) override;
     friend class ReadSorter;
@@ -243,8 +256,11 @@ protected:
 };
 
 // The multi-GPU form of ReadSorter (+ MarkDuplicates) and of a standalone MarkDuplicates: the batch
-// is cut into G contiguous input ranges, one per rank, and oge_sort_markdup_dist leaves b.slices.
-int run_ranks(ChainContext &cc, ReadBatch &b, bool sort, const oge_markdup_opts *opts, uint64_t *n_dup);
+// is cut into G contiguous input ranges, one per rank, and oge_sort_markdup_dist leaves b.slices.  With `metrics`
+// (n_lib entries, added to) every rank counts its own output slice and the host sums; *metrics_ms += the slowest
+// rank's stage time.
+int run_ranks(ChainContext &cc, ReadBatch &b, bool sort, const oge_markdup_opts *opts, uint64_t *n_dup,
+              std::vector<OgeDupMetrics> *metrics = nullptr, double *metrics_ms = nullptr);
 
 // FileWriter (algorithms/file_writer.cpp:45-196): BAM output, @PG record unless --nopg, BGZF at the
 // given level, bin recomputed on every record; SAM text, and FASTQ text to stdout, formatted on the device
@@ -303,6 +319,11 @@ int coverage_bam_file(ChainContext &cc, const std::string &path, const std::stri
 // same loader, one call (oge_bam_targets_dev, or oge_targets_dev on the records of a SAM file), the text as the
 // device wrote it to out ("stdout": standard output)
 int targets_bam_file(ChainContext &cc, const std::string &path, const std::string &out, int max_interval, int gap);
+
+// `openge dupmetrics [-o out.txt] in.bam|in.sam`: the duplication metrics of a file that is already marked, by this
+// tool or another: the file into HBM through the same loader, one call (oge_bam_dup_metrics_dev, or
+// oge_dup_metrics_dev on the records of a SAM file), the text of oge_dup_metrics_text to out ("stdout": standard output)
+int dupmetrics_bam_file(ChainContext &cc, const std::string &path, const std::string &out, const std::string &command_line);
 
 // `openge compare [-r REGION]... [-p] ref.bam other.bam [more...]` (commands/command_compare.cpp): every input
 // through a FileReader into its own batch in HBM, file 0 resident while the others come and go; the regions

@@ -11,6 +11,9 @@
 #include "../../include/openge_hip.h"
 #include "capi_common.h"
 
+// the struct by a name of its own: the plain name is the host-buffer entry point's
+using OgeDupMetrics = struct oge_dup_metrics;
+
 struct OgeStageTimer {
     hipEvent_t start, stop;
 };
@@ -82,6 +85,8 @@ struct oge_ctx {
     OgeContigTable text_table{"text_names", "text_name_off", nullptr, "text_table_uploads"};
     OgeContigTable sam_table{"sam_names", "sam_name_off", "sam_slots", "sam_table_uploads"};
     OgeContigTable targets_table{"tg_names", "tg_name_off", nullptr, "targets_table_uploads"};  // oge_targets_dev's
+    std::vector<OgeDupMetrics> dm_out;  // what the last oge_bam_dup_metrics_dev call returned
+    std::string dm_names;
     std::vector<uint8_t> sam_out_recs, sam_out_warn;
     std::vector<uint64_t> sam_out_off;
     std::map<std::string, uint64_t> counters;  // per call: work counts a stage reports (oge_ctx_counter)
@@ -235,6 +240,11 @@ int oge_qc_coverage_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_
 int oge_targets_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref, const int32_t *ref_len,
                      const char *ref_names, uint64_t names_bytes, const oge_targets_opts *opts, oge_targets_result *result,
                      const oge_target **d_targets, const uint8_t **d_text);
+
+// ---- duplication metrics (dupmetrics.hip) ----
+// oge_dup_metrics_dev without the context checks and the timing reset (oge_bam_dup_metrics_dev calls it under its hold)
+int oge_dup_metrics_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_markdup_opts *opts, int32_t n_lib,
+                         OgeDupMetrics *out);
 
 // ---- multi-GPU internals (dist.hip)
 oge_ctx *oge_comm_ctx(oge_comm *comm);

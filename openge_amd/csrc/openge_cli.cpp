@@ -17,6 +17,9 @@
 // `targets` (not in the reference, whose comments send the user to GATK's RealignerTargetCreator) computes the
 // intervals file localrealign -L takes from the reads' own indels (targets_bam_file, csrc/targets.hip; DESIGN.md
 // section 25); `localrealign --auto-targets` computes the same intervals from the records it is handed.
+// `dedup --metrics FILE` and `mergesort -M --metrics FILE` also write Picard MarkDuplicates' metrics file, which the
+// reference never wrote (algorithms/mark_duplicates.cpp has no metrics code); `dupmetrics` writes it for a file that
+// is already marked (dupmetrics_bam_file, csrc/dupmetrics.hip).
 //
 // Deliberate differences: view -B/-E cuts QUAL to the window of SEQ; the reference cuts the
 // qualities of the already shortened read a second time (algorithms/filter.cpp:188-189), which leaves fewer
@@ -70,8 +73,9 @@ const Opt kGlobal[] = {{"v", "verbose", false}, {"t", "threads", true}, {"d", "n
 const Opt kMergesort[] = {{"o", "out", true}, {"r", "region", true},  {"q", "mapq", true},
                           {"b", "byname", false}, {"n", "n", true}, {"C", "compresstempfiles", false},
                           {"M", "markduplicates", false}, {"R", "removeduplicates", false}, {"", "index", false},
-                          {"L", "regions", true}, {"", "noindex", false}};
-const Opt kDedup[] = {{"o", "out", true}, {"r", "remove", false}, {"", "index", false}};
+                          {"L", "regions", true}, {"", "noindex", false}, {"", "metrics", true}};
+const Opt kDedup[] = {{"o", "out", true}, {"r", "remove", false}, {"", "index", false}, {"", "metrics", true}};
+const Opt kDupmetrics[] = {{"o", "out", true}};
 const Opt kView[] = {{"o", "out", true}, {"n", "count", true}, {"q", "mapq", true}, {"l", "length", true},
                      {"B", "trimbegin", true}, {"E", "trimend", true}, {"r", "region", true}, {"L", "regions", true},
                      {"", "noindex", false}};
@@ -141,7 +145,7 @@ bool parse(int argc, const char **argv, const std::vector<Opt> &opts, Parsed &p)
 
 void usage_top() {
     fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, view, index, stats, count, coverage,\n"
-                    "          compare, targets, version\n"
+                    "          compare, targets, dupmetrics, version\n"
                     "\n    Inputs are BAM files or SAM text (first byte '@'; also on stdin, and mixed with BAM files); SAM is parsed\n"
                     "    on the GPU.  index takes BAM only.\n"
                     "\n    openge view [-o out] [-n N] [-q MAPQ] [-l LEN] [-r REGION] [-L FILE] [-B N] [-E N] in.bam|in.sam\n"
@@ -175,6 +179,15 @@ void usage_top() {
                     "    openge localrealign -R ref.fa (-L targets.intervals | --auto-targets) [-T tmpdir] [-o out.bam] in.bam\n"
                     "                                        --auto-targets: the intervals of `openge targets` at its defaults,\n"
                     "                                        computed from the input's records (kept in a file in tmpdir meanwhile)\n"
+                    "    openge dedup --metrics FILE / mergesort|sort -M --metrics FILE\n"
+                    "                                        also write Picard's duplication metrics of the marked records to\n"
+                    "                                        FILE: per library the reads and pairs examined, the duplicates,\n"
+                    "                                        PERCENT_DUPLICATION, ESTIMATED_LIBRARY_SIZE, and the ROI histogram\n"
+                    "                                        when there is one library; counted on the GPU before -r / -R removes\n"
+                    "                                        anything; FILE is neither the output nor stdout\n"
+                    "    openge dupmetrics [-o out.txt] in.bam|in.sam\n"
+                    "                                        the same metrics of a file that is already marked, by this tool or\n"
+                    "                                        another (default: stdout); one file, one GPU, no stdin\n"
                     "\nGPU options (every command):\n"
                     "    --device N              first GPU\n"
                     "    --gpus G                ranks over G GPUs\n"
@@ -210,6 +223,7 @@ int main(int argc, const char **argv) {
     else if (cmd == "coverage") opts.insert(opts.end(), std::begin(kCoverage), std::end(kCoverage));
     else if (cmd == "compare") opts.insert(opts.end(), std::begin(kCompare), std::end(kCompare));
     else if (cmd == "targets") opts.insert(opts.end(), std::begin(kTargets), std::end(kTargets));
+    else if (cmd == "dupmetrics") opts.insert(opts.end(), std::begin(kDupmetrics), std::end(kDupmetrics));
     else {
         fprintf(stderr, "Unknown command %s.\n", argv[1]);
         return -1;
@@ -355,6 +369,31 @@ int main(int argc, const char **argv) {
             return -1;
         }
     }
+    if (cmd == "dupmetrics") {  // refused before anything is read
+        if (p.inputs.size() != 1 || p.inputs[0] == "stdin" || p.inputs[0] == "-") {
+            fprintf(stderr, "openge dupmetrics: one BAM or SAM file is required (stdin is not provided)\n");
+            return -1;
+        }
+        if (cc.gpus > 1) {
+            fprintf(stderr, "openge dupmetrics: --gpus is not provided\n");
+            return -1;
+        }
+    }
+    if (p.count("metrics")) {  // refused before anything is read
+        const std::string mf = p.get("metrics", "");
+        if (cmd == "mergesort" && !p.count("markduplicates") && !p.count("removeduplicates")) {
+            fprintf(stderr, "openge mergesort: --metrics needs -M or -R (there is nothing to count without the duplicate marking)\n");
+            return -1;
+        }
+        if (mf.empty() || mf == "stdout" || mf == "-") {
+            fprintf(stderr, "openge %s: --metrics needs a file name (stdout is not provided)\n", cmd.c_str());
+            return -1;
+        }
+        if (mf == out_name) {
+            fprintf(stderr, "openge %s: --metrics names the output file\n", cmd.c_str());
+            return -1;
+        }
+    }
     if (cmd == "localrealign" && p.count("auto-targets") && p.count("intervals")) {
         fprintf(stderr, "openge localrealign: -L and --auto-targets exclude each other\n");
         return -1;
@@ -398,6 +437,11 @@ int main(int argc, const char **argv) {
     if (cmd == "targets") {
         const int r = targets_bam_file(cc, p.inputs[0], p.get("out", "stdout"), atoi(p.get("maxinterval", "500").c_str()),
                                        atoi(p.get("gap", "0").c_str()));
+        oge_ctx_destroy(cc.ctx);
+        return r;
+    }
+    if (cmd == "dupmetrics") {
+        const int r = dupmetrics_bam_file(cc, p.inputs[0], p.get("out", "stdout"), command_line);
         oge_ctx_destroy(cc.ctx);
         return r;
     }
@@ -456,6 +500,8 @@ int main(int argc, const char **argv) {
             md.removeDuplicates = p.count("removeduplicates");
             md.compatNonverbose = compat;
             md.splitChains = split;
+            md.metricsFilename = p.get("metrics", "");
+            md.metricsCommandLine = command_line;
             sorter.addSink(&md);
             md.addSink(&writer);
         } else {
@@ -468,6 +514,8 @@ int main(int argc, const char **argv) {
         md.removeDuplicates = p.count("remove");
         md.compatNonverbose = compat;
         md.splitChains = split;
+        md.metricsFilename = p.get("metrics", "");
+        md.metricsCommandLine = command_line;
         reader.addSink(&md);
         md.addSink(&writer);
         ret = writer.runChain(cc);

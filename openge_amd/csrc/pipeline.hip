@@ -378,6 +378,38 @@ extern "C" int oge_bam_targets_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zb
                             result, d_targets, d_text);
 }
 
+extern "C" int oge_bam_dup_metrics_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const OgeDupMetrics **out, int32_t *n_lib,
+                                       const char **lib_names, uint64_t *names_bytes, int32_t *unknown_lib) {
+    if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
+    if (!out || !n_lib || !lib_names || !names_bytes || !unknown_lib || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
+    OgeCall call(ctx, /*hold=*/true);
+    *out = nullptr;
+    *n_lib = 0;
+    uint8_t *X;
+    uint64_t *xoff, n;
+    BamFile f;
+    int rc = decode_for_qc(ctx, d_z, zbytes, &X, &xoff, &n, &f);
+    if (rc) return rc;
+    oge_mergesort_opts mo;
+    oge_mergesort_opts_init(&mo);
+    const LibTable lt(f.header, (int32_t)f.ref_names.size(), &mo);
+    int16_t top = lt.o.unknown_lib;
+    for (size_t g = 0; g < f.header.rg.size(); ++g) top = std::max(top, lt.libs[g]);
+    std::vector<std::string> names((size_t)top + 1);
+    for (size_t g = 0; g < f.header.rg.size(); ++g) names[lt.libs[g]] = f.header.rg[g].lb.empty() ? std::string("Unknown Library") : f.header.rg[g].lb;
+    ctx->dm_out.assign((size_t)top + 1, OgeDupMetrics{});
+    ctx->dm_names.clear();
+    for (const std::string &s : names) ctx->dm_names.append(s.c_str(), s.size() + 1);
+    rc = oge_dup_metrics_impl(ctx, X, xoff, n, &lt.o, (int32_t)top + 1, ctx->dm_out.data());
+    if (rc) return rc;
+    *out = ctx->dm_out.data();
+    *n_lib = (int32_t)top + 1;
+    *lib_names = ctx->dm_names.data();
+    *names_bytes = ctx->dm_names.size();
+    *unknown_lib = lt.o.unknown_lib;
+    return OGE_OK;
+}
+
 extern "C" int oge_bam_count_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint64_t *n_reads) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!n_reads || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");

@@ -381,6 +381,11 @@ def lib() -> C.CDLL:
         "oge_targets_dev": (C.c_int, [vp, vp, vp, u64, i32, vp, C.c_char_p, u64, vp, vp, C.POINTER(vp), C.POINTER(vp)]),
         "oge_targets": (C.c_int, [vp, vp, u64, vp, u64, i32, vp, C.c_char_p, u64, vp, vp, vp, u64, vp, u64]),
         "oge_bam_targets_dev": (C.c_int, [vp, vp, u64, vp, vp, C.POINTER(vp), C.POINTER(vp)]),
+        "oge_dup_metrics_dev": (C.c_int, [vp, vp, vp, u64, vp, i32, vp]),
+        "oge_dup_metrics": (C.c_int, [vp, vp, u64, vp, u64, vp, i32, vp]),
+        "oge_bam_dup_metrics_dev": (C.c_int, [vp, vp, u64, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(u64), C.POINTER(i32)]),
+        "oge_estimate_library_size": (C.c_int, [u64, u64, C.POINTER(u64)]),
+        "oge_dup_metrics_text": (C.c_int, [vp, vp, i32, C.c_char_p, vp, u64, C.POINTER(u64)]),
         "oge_bam_stats_dev": (C.c_int, [vp, vp, u64, u32, vp, C.POINTER(vp), C.POINTER(vp)]),
         "oge_bam_coverage_dev": (C.c_int, [vp, vp, u64, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]),
         "oge_bam_count_dev": (C.c_int, [vp, vp, u64, C.POINTER(u64)]),
@@ -433,6 +438,27 @@ def infl_plan(nblk: int, lanes: int, budget: int, max_per_lane: int = 0, balance
     sizes = np.zeros(max(n, 1), dtype=np.uint64)
     lib().oge_infl_plan(nblk, lanes, budget, max_per_lane, int(balanced), _ptr(sizes), n)
     return [int(x) for x in sizes[:n]]
+
+
+def estimate_library_size(pairs: int, unique_pairs: int) -> int | None:
+    """oge_estimate_library_size (host only): Picard's estimate, None when there is none."""
+    size = C.c_uint64()
+    return None if lib().oge_estimate_library_size(pairs, unique_pairs, C.byref(size)) else size.value
+
+
+def dup_metrics_text(rows, command_line: str, cap: int | None = None) -> bytes:
+    """oge_dup_metrics_text (host only): rows = [(library name, the six counters of oge_dup_metrics)] -> the
+    metrics file.  cap: the buffer of the second call (default: the size the first call reports, + 1 for the NUL);
+    a smaller one gets the text cut to cap - 1 bytes."""
+    names = [nm.encode() if isinstance(nm, str) else bytes(nm) for nm, _ in rows]
+    arr = (C.c_char_p * max(len(rows), 1))(*names)
+    m = np.array([list(c6) for _, c6 in rows] or [[0] * 6], dtype=np.uint64)
+    need = C.c_uint64()
+    check(lib().oge_dup_metrics_text(arr, _ptr(m), len(rows), command_line.encode(), None, 0, C.byref(need)))
+    cap = need.value + 1 if cap is None else cap
+    buf = C.create_string_buffer(max(cap, 1))
+    check(lib().oge_dup_metrics_text(arr, _ptr(m), len(rows), command_line.encode(), buf, cap, C.byref(need)))
+    return buf.raw[:min(max(cap, 1) - 1, need.value)]
 
 
 def exported_symbols() -> list[str]:
@@ -857,6 +883,31 @@ class Context:
             o, res, dt, dx = self._targets_opts(max_interval, gap), TargetsResult(), C.c_void_p(), C.c_void_p()
             check(lib().oge_bam_targets_dev(self.h, dz, nbytes, C.byref(o), C.byref(res), C.byref(dt), C.byref(dx)), self.h)
             return self._targets_out(res, dt, dx)
+        return self._with_file(data, run)
+
+    # ---- duplication metrics (csrc/dupmetrics.hip)
+    def dup_metrics_dev(self, d_recs, d_off, n: int, opts: MarkdupOpts, n_lib: int) -> np.ndarray:
+        """oge_dup_metrics_dev on device records -> uint64 (n_lib, 6): the fields of oge_dup_metrics by library id."""
+        out = np.full((max(n_lib, 1), 6), 0xDEADBEEF, np.uint64)  # the call sets it
+        check(lib().oge_dup_metrics_dev(self.h, d_recs, d_off, n, C.byref(opts), n_lib, _ptr(out)), self.h)
+        return out[:n_lib]
+
+    def dup_metrics(self, recs: np.ndarray, offs: np.ndarray, n: int, opts: MarkdupOpts, n_lib: int) -> np.ndarray:
+        """oge_dup_metrics: the same from host buffers (recs with 16 bytes of slack behind the last record)."""
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        out = np.full((max(n_lib, 1), 6), 0xDEADBEEF, np.uint64)
+        check(lib().oge_dup_metrics(self.h, _ptr(recs), max(recs.nbytes - 16, 0), _ptr(offs), n, C.byref(opts), n_lib, _ptr(out)), self.h)
+        return out[:n_lib]
+
+    def bam_dup_metrics(self, data: bytes) -> tuple[np.ndarray, list[str], int]:
+        """`openge dupmetrics` of a whole BAM file (oge_bam_dup_metrics_dev on a copy of the file in HBM) -> (the
+        counters (n_lib, 6), the library names by id, "" where no @RG names the id, unknown_lib)."""
+        def run(dz, nbytes):
+            po, n, pn, nb, unk = C.c_void_p(), C.c_int32(), C.c_void_p(), C.c_uint64(), C.c_int32()
+            check(lib().oge_bam_dup_metrics_dev(self.h, dz, nbytes, C.byref(po), C.byref(n), C.byref(pn), C.byref(nb), C.byref(unk)), self.h)
+            out = np.frombuffer(C.string_at(po.value, 48 * n.value), np.uint64).reshape(n.value, 6).copy()
+            names = C.string_at(pn.value, nb.value).split(b"\0")[:n.value]
+            return out, [x.decode() for x in names], unk.value
         return self._with_file(data, run)
 
     # ---- SAM / FASTQ text (csrc/sam.hip)
