@@ -1009,6 +1009,20 @@ uint64_t bits_mask_hi32(uint64_t n) {
 
 }  // namespace
 
+// The field widths of the packed group keys (md_keys.h): sb bits of refID, lb bits of library id.  The
+// fragment key keeps bit 46 for "not a fragment", so sb + lb + 33 may not pass 46: sb + lb <= 13.
+static int md_layout(oge_ctx *ctx, const oge_markdup_opts *opts, KeyLayout *L) {
+    int16_t maxlib = opts->unknown_lib;
+    for (int32_t g = 0; g < opts->n_rg; ++g) maxlib = std::max(maxlib, opts->rg_lib[g]);
+    if (opts->unknown_lib < 0) return oge_fail(ctx, OGE_ERR_ARG, "markdup: negative library id");
+    for (int32_t g = 0; g < opts->n_rg; ++g)
+        if (opts->rg_lib[g] < 0) return oge_fail(ctx, OGE_ERR_ARG, "markdup: negative library id");
+    *L = KeyLayout{bits_for((uint64_t)std::max(opts->n_ref, 1)), bits_for((uint64_t)maxlib), opts->split_chains};
+    if (L->sb + L->lb + 34 > 47 || L->sb + L->lb > 16)
+        return oge_fail(ctx, OGE_ERR_LIMIT, "markdup: too many references x libraries for the packed group key");
+    return OGE_OK;
+}
+
 // Allocate the per-record ReadEnds summaries (`name` selects the buffer) and upload the RG table.
 int oge_markdup_prepare(oge_ctx *ctx, const oge_markdup_opts *opts, uint64_t n, const char *name, RecMeta **meta,
                         OgeRgTable *rg) {
@@ -1021,6 +1035,10 @@ int oge_markdup_prepare(oge_ctx *ctx, const oge_markdup_opts *opts, uint64_t n, 
     if (opts->n_rg < 0 || (opts->n_rg && (!opts->rg_ids || !opts->rg_lib)))
         return oge_fail(ctx, OGE_ERR_ARG, "markdup: bad read-group table");
     if (opts->n_rg > OGE_MAX_RG) return oge_fail(ctx, OGE_ERR_LIMIT, "markdup: more than 32767 read groups");
+    // refuse a layout the group keys cannot hold here, before any pass has written a buffer of the caller's
+    // (the fused chain's output arena is lent out as scratch, and its stages check the layout only later)
+    KeyLayout L0;
+    if (int lrc = md_layout(ctx, opts, &L0)) return lrc;
     *meta = (RecMeta *)(strcmp(name, "md_meta_in") ? ctx->ws(name, (n + 1) * sizeof(RecMeta))
                                                    : ctx->scratch(name, (n + 1) * sizeof(RecMeta)));
     std::vector<uint32_t> offs(opts->n_rg + 1, 0);
@@ -1078,18 +1096,6 @@ int oge_md_pairs_rehash(oge_ctx *ctx, OgeMdPairs *P) {
 // ------------------------------------------------------------------------------------ stages
 // oge_markdup_finish is the sequence cand_frag -> join_build -> pair_groups -> frag_groups -> apply;
 // the multi-GPU path (dist.hip) runs the same stages on ReadEnds exchanged between ranks.
-
-static int md_layout(oge_ctx *ctx, const oge_markdup_opts *opts, KeyLayout *L) {
-    int16_t maxlib = opts->unknown_lib;
-    for (int32_t g = 0; g < opts->n_rg; ++g) maxlib = std::max(maxlib, opts->rg_lib[g]);
-    if (opts->unknown_lib < 0) return oge_fail(ctx, OGE_ERR_ARG, "markdup: negative library id");
-    for (int32_t g = 0; g < opts->n_rg; ++g)
-        if (opts->rg_lib[g] < 0) return oge_fail(ctx, OGE_ERR_ARG, "markdup: negative library id");
-    *L = KeyLayout{bits_for((uint64_t)std::max(opts->n_ref, 1)), bits_for((uint64_t)maxlib), opts->split_chains};
-    if (L->sb + L->lb + 34 > 47 || L->sb + L->lb > 16)
-        return oge_fail(ctx, OGE_ERR_LIMIT, "markdup: too many references x libraries for the packed group key");
-    return OGE_OK;
-}
 
 static CandKey md_candkey(const oge_markdup_opts *opts, uint64_t n) {
     CandKey ckl;

@@ -14,7 +14,7 @@ regenerated header text.  Inputs are either fixtures the reference's own tests h
 (openge/test/data/*.bam, copied into inputs/) or deterministic synthetic sets rebuilt from their
 parameters at test time.
 
-Usage:  python tests/golden/make_goldens.py
+Usage:  python tests/golden/make_goldens.py [case ...]     (no names: every case)
 """
 from __future__ import annotations
 
@@ -35,6 +35,7 @@ sys.path.insert(0, str(ROOT / "tests"))
 
 import bamutil  # noqa: E402
 import oracle  # noqa: E402
+import markdup_wide_cases  # noqa: E402
 from golden.edge_cases import HEADER as EDGE_HEADER, REFS as EDGE_REFS, build_edge_records  # noqa: E402
 from openge_amd import lib as L  # noqa: E402
 
@@ -46,6 +47,7 @@ CASES = {
     "mix3k": {"kind": "synth", "preset": "mix", "n_pairs": 3000, "seed": 7},
     "c2_20k": {"kind": "synth", "preset": "c2", "n_pairs": 20000, "seed": 99},
     "c1_100k": {"kind": "synth", "preset": "c1", "n_pairs": 50000, "seed": 1234},
+    "wide2047": {"kind": "wide", "set": "w13a"},  # 2047 contigs x 3 libraries: the packed group key at its limit
 }
 FULL_ARRAYS_MAX = 20000
 SPLIT_K = (3, 12)
@@ -62,6 +64,10 @@ def materialize(name: str, spec: dict, tmp: Path) -> Path:
     path = tmp / f"{name}.bam"
     if spec["kind"] == "edge":
         bamutil.write_bam_py(path, EDGE_HEADER, EDGE_REFS, build_edge_records())
+        return path
+    if spec["kind"] == "wide":
+        w = markdup_wide_cases.get(spec["set"])
+        bamutil.write_bam_py(path, w.header, w.refs, w.records)
         return path
     p = L.synth_params(spec["n_pairs"], preset=spec["preset"], seed=spec["seed"])
     recs, offs, hdr = L.synth_host(p)
@@ -88,12 +94,16 @@ def run(driver, mode, src, dst, *extra):
                    capture_output=True, timeout=600)
 
 
-def main():
+def main(only=()):
+    unknown = [c for c in only if c not in CASES]
+    assert not unknown, f"no such case: {unknown}"
     driver = oracle.build_ref()
     assert driver and driver.exists(), "reference harness could not be built"
     with tempfile.TemporaryDirectory() as td:
         tmp = Path(td)
         for name, spec in CASES.items():
+            if only and name not in only:
+                continue
             src = materialize(name, spec, tmp)
             out = HERE / name
             out.mkdir(exist_ok=True)
@@ -134,4 +144,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

@@ -12,7 +12,7 @@ import bamutil
 from golden.edge_cases import HEADER as EDGE_HEADER, build_edge_records
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
-CASE_NAMES = ["simple", "yhet208", "edge", "mix3k", "c2_20k", "c1_100k"]
+CASE_NAMES = ["simple", "yhet208", "edge", "mix3k", "c2_20k", "c1_100k", "wide2047"]
 
 
 @dataclass
@@ -40,6 +40,11 @@ def load_case(name: str) -> Case:
         header = EDGE_HEADER
         recs, offs = bamutil.pack_records(build_edge_records())
         n_ref = 2
+    elif spec["kind"] == "wide":
+        import markdup_wide_cases
+        w = markdup_wide_cases.get(spec["set"])
+        header, n_ref = w.header, w.n_ref
+        recs, offs = bamutil.pack_records(w.records)
     else:
         from openge_amd import lib as L
         p = L.synth_params(spec["n_pairs"], preset=spec["preset"], seed=spec["seed"])
