@@ -780,6 +780,69 @@ int oge_estimate_library_size(uint64_t pairs, uint64_t unique_pairs, uint64_t *s
 int oge_dup_metrics_text(const char *const *names, const struct oge_dup_metrics *m, int32_t n_rows, const char *command_line, char *buf,
                          uint64_t cap, uint64_t *len_out);
 
+/* ---- duplicate sets: optical duplicates and set-size histograms (--optical-distance N) ------------------------
+ * What the six counters above cannot give: the pair duplicate SETS of records resident in HBM, per library their
+ * optical duplicates, over all libraries three set-size histograms.  DESIGN.md section 27; the model is
+ * tests/dupsets_model.py.  Picard is not part of the tests: no byte parity with it is claimed.
+ * Pairs and sets are exactly the dedup's: ReadEnds of mapped primary records, the ends of one RG:name paired up
+ *   consecutively in record order, a set = the pairs with equal (library, read-1 refID, read-1 5' coordinate,
+ *   orientation, read-2 refID, read-2 5' coordinate); a set of one pair is a set.  The duplicate flags are not
+ *   read: a marked and an unmarked file give the same result, in any record order that keeps each name's ends in
+ *   their relative order.
+ * Location of a pair, from the name of its read 1 (the leftmost end; the bytes before the NUL): split at ':'; with
+ *   exactly 5 or exactly 7 fields the last three are tile, x, y; any other count: no location.  A number is an
+ *   optional '-', then decimal digits up to the first other byte (trailing bytes are ignored, no digit gives 0),
+ *   held in int32 (the result of more than 9 digits is not defined).  The tile is kept as int32 (Picard narrows it
+ *   to 16 bits: a stated departure).  The read group is the index g the RG walk above resolves read 1's value to
+ *   (the first @RG of that id), or -1.
+ * Optical duplicates of a set: a set whose orientation is FR or RF (the two ends on different strands) is first
+ *   divided in two by whether read 1 has FLAG 0x40; FF and RR sets are not divided.  Within a part two located
+ *   pairs are close when they have the same read-group index and tile, |dx| <= D and |dy| <= D; the part
+ *   contributes (located members) - (connected components of "close"); the sum over the parts goes to the set's
+ *   library.
+ * Histograms: OGE_DUP_SETS_BINS u64 bins per column, a value counted at min(value, bins - 1), all libraries
+ *   together, every set counted: for a set of s pairs with o optical duplicates all_sets[s]++,
+ *   non_optical_sets[s - o]++, and optical_sets[o + 1]++ when o > 0.  hist holds the three columns one after the
+ *   other in that order of the text: all_sets, optical_sets, non_optical_sets.
+ * Per library: pairs, sets, optical, and located = the pairs with a location in sets of two or more pairs (the
+ *   only ones whose names are read).  pairs - sets equals READ_PAIR_DUPLICATES of the marked records unless a
+ *   candidate end has a mate refID of -1.
+ * The pass repeats the dedup's ReadEnds pass and mate join (no kernel of theirs is changed), groups the pairs
+ * exactly (two stable radix sorts on the varying key bits, head flags, a scan), reads the names of the members of
+ * sets of two or more, and counts components in three tiers: sets of at most "dupsets_wave_cap" (64) members in a
+ * wave, whole sets only; larger ones up to "dupsets_block_cap" in one workgroup's LDS; larger ones by an exact
+ * union-find on the host ("dupsets_host_sets").  Counters "dupsets_wave_sets" and "dupsets_block_sets" count the
+ * sets of two or more pairs the first two tiers took.  Stage "dup_sets", with sub-stages "ds_readends", "ds_join",
+ * "ds_group", "ds_locate", "ds_components".
+ * OGE_ERR_LIMIT: n >= 2^31, n_lib > 2048.  OGE_ERR_ARG: distance < 0, a library id outside [0, n_lib). */
+#define OGE_DUP_SETS_BINS 1024
+struct oge_dup_sets_lib {
+    uint64_t pairs, sets, located, optical;
+};
+/* Records as for oge_dup_metrics_dev; opts as for oge_markdup_dev (the read-group table and n_ref; split_chains
+ * must be <= 1 and compat_nonverbose_index 0).  out_per_lib[n_lib] and hist[3 * OGE_DUP_SETS_BINS] are SET.
+ * Synchronous on the context's stream. */
+int oge_dup_sets_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_markdup_opts *opts,
+                     int64_t distance, int32_t n_lib, struct oge_dup_sets_lib *out_per_lib, uint64_t *hist);
+/* Host-buffer form: uploads the records and offsets, then the same. */
+int oge_dup_sets(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const uint64_t *rec_off, uint64_t n,
+                 const oge_markdup_opts *opts, int64_t distance, int32_t n_lib, struct oge_dup_sets_lib *out_per_lib, uint64_t *hist);
+/* A whole BAM file resident in HBM, as oge_bam_dup_metrics_dev: the libraries numbered from the file's own header.
+ * *out_per_lib (*n_lib entries) and *hist (3 * OGE_DUP_SETS_BINS) are host memory of the context, valid until its
+ * next call of this function. */
+int oge_bam_dup_sets_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, int64_t distance, const struct oge_dup_sets_lib **out_per_lib,
+                         const uint64_t **hist, int32_t *n_lib);
+/* The metrics file with the optical column filled and the set-size histogram, host only.  Rows as for
+ * oge_dup_metrics_text, s[i] beside m[i]: READ_PAIR_OPTICAL_DUPLICATES = s[i].optical, ESTIMATED_LIBRARY_SIZE =
+ * oge_estimate_library_size(READ_PAIRS_EXAMINED - optical, READ_PAIRS_EXAMINED - READ_PAIR_DUPLICATES) (none when
+ * optical or the duplicates exceed the pairs), the ROI from the same two arguments.  The histogram block is always
+ * written: "## HISTOGRAM<TAB>java.lang.Double", the column line BIN, then CoverageMult only with exactly one row
+ * that has an estimate above 0, then all_sets, optical_sets, non_optical_sets; one line per BIN from 1 to the
+ * largest non-empty bin of the three columns (to 100 if the ROI column is there and that is larger; past 100 the
+ * ROI continues by the same formula); BIN as "%d.0", the ROI as %.6f, the counts as integers; a blank line. */
+int oge_dup_sets_text(const char *const *names, const struct oge_dup_metrics *m, const struct oge_dup_sets_lib *s, int32_t n_rows,
+                      const uint64_t *hist, const char *command_line, char *buf, uint64_t cap, uint64_t *len_out);
+
 /* ---- SAM and FASTQ text of records in HBM (openge view, -F sam|fastq) ----------------------------------
  * The reference's SamWriter::write (util/sam_writer.cpp:90-217) and the single-stream form of
  * FastqWriter::write (util/fastq_writer.cpp:99-100) on the device; DESIGN.md section 21.

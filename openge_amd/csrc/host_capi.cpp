@@ -262,6 +262,72 @@ extern "C" int oge_dup_metrics_text(const char *const *names, const struct oge_d
     return OGE_OK;
 }
 
+// The same file with the optical column filled and the set-size histogram (--optical-distance; DESIGN.md section 27,
+// tests/dupsets_model.py).  oge_dup_metrics_text stays as it is: without the option every byte is the one it wrote.
+extern "C" int oge_dup_sets_text(const char *const *names, const struct oge_dup_metrics *m, const struct oge_dup_sets_lib *s, int32_t n_rows,
+                                 const uint64_t *hist, const char *command_line, char *buf, uint64_t cap, uint64_t *len_out) {
+    if (n_rows < 0 || (n_rows && (!names || !m || !s)) || !hist || !command_line) return oge_fail(nullptr, OGE_ERR_ARG, "oge_dup_sets_text: null argument");
+    std::vector<int32_t> order(n_rows);
+    for (int32_t i = 0; i < n_rows; ++i) {
+        if (!names[i]) return oge_fail(nullptr, OGE_ERR_ARG, "oge_dup_sets_text: null name");
+        order[i] = i;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return strcmp(names[a], names[b]) < 0; });
+    std::string t = "## htsjdk.samtools.metrics.StringHeader\n# ";
+    t += command_line;
+    t += "\n\n## METRICS CLASS\tpicard.sam.DuplicationMetrics\n"
+         "LIBRARY\tUNPAIRED_READS_EXAMINED\tREAD_PAIRS_EXAMINED\tSECONDARY_OR_SUPPLEMENTARY_RDS\tUNMAPPED_READS\tUNPAIRED_READ_DUPLICATES\t"
+         "READ_PAIR_DUPLICATES\tREAD_PAIR_OPTICAL_DUPLICATES\tPERCENT_DUPLICATION\tESTIMATED_LIBRARY_SIZE\n";
+    char num[64];
+    uint64_t pairs = 0, dup_pairs = 0, optical = 0, size = 0;
+    bool has_size = false;
+    for (int32_t i : order) {
+        const struct oge_dup_metrics &x = m[i];
+        pairs = x.pair_reads_examined / 2;
+        dup_pairs = x.pair_read_dups / 2;
+        optical = s[i].optical;
+        const uint64_t den = x.unpaired_examined + x.pair_reads_examined;
+        const double pct = den ? (double)(x.unpaired_dups + x.pair_read_dups) / (double)den : 0.0;
+        // more optical duplicates or more duplicates than pairs: no estimate
+        has_size = optical <= pairs && dup_pairs <= pairs && oge_estimate_library_size(pairs - optical, pairs - dup_pairs, &size) == 0;
+        t += names[i];
+        for (uint64_t v : {x.unpaired_examined, pairs, x.secondary, x.unmapped, x.unpaired_dups, dup_pairs, optical}) t += "\t" + std::to_string(v);
+        snprintf(num, sizeof num, "\t%.6f\t", pct);
+        t += num;
+        if (has_size) t += std::to_string(size);
+        t += "\n";
+    }
+    t += "\n";
+    const bool roi = n_rows == 1 && has_size && size;
+    int last = 0;
+    for (int k = 1; k < OGE_DUP_SETS_BINS; ++k)
+        if (hist[k] || hist[OGE_DUP_SETS_BINS + k] || hist[2 * OGE_DUP_SETS_BINS + k]) last = k;
+    if (roi && last < 100) last = 100;
+    t += "## HISTOGRAM\tjava.lang.Double\nBIN";
+    if (roi) t += "\tCoverageMult";
+    t += "\tall_sets\toptical_sets\tnon_optical_sets\n";
+    const double L = (double)size, n = (double)(pairs - optical), c = (double)(pairs - dup_pairs);
+    for (int k = 1; k <= last; ++k) {
+        snprintf(num, sizeof num, "%d.0", k);
+        t += num;
+        if (roi) {
+            const double x = (double)k;
+            snprintf(num, sizeof num, "\t%.6f", L * (1 - exp(-(x * n) / L)) / c);
+            t += num;
+        }
+        for (int col = 0; col < 3; ++col) t += "\t" + std::to_string(hist[col * OGE_DUP_SETS_BINS + k]);
+        t += "\n";
+    }
+    t += "\n";
+    if (len_out) *len_out = t.size();
+    if (buf && cap) {
+        const size_t k = std::min<size_t>(cap - 1, t.size());
+        memcpy(buf, t.data(), k);
+        buf[k] = 0;
+    }
+    return OGE_OK;
+}
+
 // ----------------------------------------------------------------------------- Filter (mergesort -r/-q)
 extern "C" void oge_filter_opts_init(oge_filter_opts *o) {  // Filter::Filter (filter.cpp:185-194)
     if (!o) return;

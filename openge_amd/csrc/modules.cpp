@@ -1046,6 +1046,12 @@ static void metrics_begin(MarkDuplicates *md, const MdOpts &m) {
     md->metricsUnknown = m.o.unknown_lib;
     md->metrics.assign(m.lib_names.size(), OgeDupMetrics{});
     md->metricsMs = 0;
+    if (md->opticalDistance >= 0) {
+        md->sets.assign(m.lib_names.size(), OgeDupSetsLib{});
+        md->setsHist.assign(3 * OGE_DUP_SETS_BINS, 0);
+        md->setsMs = 0;
+        md->setsTiers[0] = md->setsTiers[1] = md->setsTiers[2] = 0;
+    }
 }
 static int metrics_count(MarkDuplicates *md, oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_offs, uint64_t n, const MdOpts &m) {
     std::vector<OgeDupMetrics> part(md->metrics.size());
@@ -1053,25 +1059,45 @@ static int metrics_count(MarkDuplicates *md, oge_ctx *ctx, const uint8_t *d_recs
     for (size_t k = 0; k < part.size(); ++k) add_metrics(md->metrics[k], part[k]);
     double ms = 0;
     if (!oge_ctx_timing(ctx, "dup_metrics", &ms) && ms > 0) md->metricsMs += ms;
+    if (md->opticalDistance < 0) return 0;
+    // --optical-distance: the duplicate sets of the same records, which are all resident here
+    if (oge_dup_sets_dev(ctx, d_recs, d_offs, n, &m.o, md->opticalDistance, (int32_t)md->sets.size(), md->sets.data(), md->setsHist.data())) return -1;
+    if (!oge_ctx_timing(ctx, "dup_sets", &ms) && ms > 0) md->setsMs = ms;
+    const char *tiers[3] = {"dupsets_wave_sets", "dupsets_block_sets", "dupsets_host_sets"};
+    for (int k = 0; k < 3; ++k) oge_ctx_counter(ctx, tiers[k], &md->setsTiers[k]);
     return 0;
 }
 
 // One row for every library an @RG names, one more "Unknown Library" row when none does and a record resolved to it
 // (names by library id, "" = not named); oge_dup_metrics_text sorts them.
+// sets / hist (--optical-distance; sets by library id as m): the text of oge_dup_sets_text
 static int metrics_text(const std::vector<std::string> &names, int unknown, const std::vector<OgeDupMetrics> &m, const std::string &command_line,
-                        std::string &text) {
+                        std::string &text, const std::vector<OgeDupSetsLib> *sets = nullptr, const uint64_t *hist = nullptr) {
     std::vector<const char *> row_names;
     std::vector<OgeDupMetrics> rows;
+    std::vector<OgeDupSetsLib> srows;
     for (size_t k = 0; k < names.size() && k < m.size(); ++k)
-        if (!names[k].empty()) row_names.push_back(names[k].c_str()), rows.push_back(m[k]);
+        if (!names[k].empty()) {
+            row_names.push_back(names[k].c_str()), rows.push_back(m[k]);
+            if (sets) srows.push_back((*sets)[k]);
+        }
     if (unknown >= 0 && (size_t)unknown < m.size() && names[unknown].empty()) {
         const OgeDupMetrics &u = m[unknown];
-        if (u.unpaired_examined | u.pair_reads_examined | u.secondary | u.unmapped | u.unpaired_dups | u.pair_read_dups)
+        if (u.unpaired_examined | u.pair_reads_examined | u.secondary | u.unmapped | u.unpaired_dups | u.pair_read_dups) {
             row_names.push_back("Unknown Library"), rows.push_back(u);
+            if (sets) srows.push_back((*sets)[unknown]);
+        }
     }
     std::string cl = command_line;
     while (!cl.empty() && cl.back() == ' ') cl.pop_back();
     uint64_t need = 0;
+    if (sets) {
+        if (oge_dup_sets_text(row_names.data(), rows.data(), srows.data(), (int32_t)rows.size(), hist, cl.c_str(), nullptr, 0, &need)) return -1;
+        text.resize(need + 1);
+        if (oge_dup_sets_text(row_names.data(), rows.data(), srows.data(), (int32_t)rows.size(), hist, cl.c_str(), &text[0], need + 1, &need)) return -1;
+        text.resize(need);
+        return 0;
+    }
     if (oge_dup_metrics_text(row_names.data(), rows.data(), (int32_t)rows.size(), cl.c_str(), nullptr, 0, &need)) return -1;
     text.resize(need + 1);
     if (oge_dup_metrics_text(row_names.data(), rows.data(), (int32_t)rows.size(), cl.c_str(), &text[0], need + 1, &need)) return -1;
@@ -1083,7 +1109,8 @@ static int write_text_file(const std::string &out, const std::vector<uint8_t> &t
 
 int MarkDuplicates::writeMetrics() const {
     std::string text;
-    if (metrics_text(metricsLibraries, metricsUnknown, metrics, metricsCommandLine, text)) {
+    const bool optical = opticalDistance >= 0;
+    if (metrics_text(metricsLibraries, metricsUnknown, metrics, metricsCommandLine, text, optical ? &sets : nullptr, optical ? setsHist.data() : nullptr)) {
         fprintf(stderr, "openge: MarkDuplicates: metrics: %s\n", oge_last_error(nullptr));
         return -1;
     }
@@ -1091,6 +1118,10 @@ int MarkDuplicates::writeMetrics() const {
     if (verbose_) fprintf(stderr, "[openge] MarkDuplicates: metrics of %zu libraries to %s, stage dup_metrics %.3f ms\n",
                           (size_t)std::count_if(metricsLibraries.begin(), metricsLibraries.end(), [](const std::string &s) { return !s.empty(); }),
                           metricsFilename.c_str(), metricsMs);
+    if (verbose_ && optical)
+        fprintf(stderr, "[openge] MarkDuplicates: duplicate sets at optical distance %lld, stage dup_sets %.3f ms, sets of two or more pairs: "
+                        "%llu in a wave, %llu in a workgroup, %llu on the host\n",
+                (long long)opticalDistance, setsMs, (unsigned long long)setsTiers[0], (unsigned long long)setsTiers[1], (unsigned long long)setsTiers[2]);
     return 0;
 }
 
@@ -1244,6 +1275,12 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
             fprintf(stderr, "[openge] ReadSorter: %d ranks, %.3f s\n", cc.gpus,
                     sec(t0, clk()));
         return 0;
+    }
+    if (order_ == BamHeaderModel::COORDINATE && use_chunked(cc, b) && md && md->opticalDistance >= 0) {
+        // the duplicate sets need every record resident in HBM at once; refused here, before the writer opens the output
+        fprintf(stderr, "openge mergesort: --optical-distance needs the records resident in HBM, and this input takes the chunked path "
+                        "(larger than HBM, or OGE_CHUNK_BYTES)\n");
+        return -1;
     }
     if (order_ == BamHeaderModel::COORDINATE && use_chunked(cc, b)) {
         // larger than HBM: sorted runs spilled into the host arena, key ranges sorted on the device,
@@ -2150,6 +2187,25 @@ struct QcInput {
         *unknown = unk;
         return 0;
     }
+    // --optical-distance: the duplicate sets, n_lib entries as dup_metrics numbered them (the same header)
+    int dup_sets(int64_t distance, int32_t n_lib, std::vector<OgeDupSetsLib> &s, std::vector<uint64_t> &hist) {
+        if (sam) {
+            MdOpts mo;
+            markdup_opts(b, false, 0, mo);
+            s.assign((size_t)n_lib, OgeDupSetsLib{});
+            hist.assign(3 * OGE_DUP_SETS_BINS, 0);
+            return oge_dup_sets_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &mo.o, distance, n_lib, s.data(), hist.data());
+        }
+        const OgeDupSetsLib *out = nullptr;
+        const uint64_t *h = nullptr;
+        int32_t got = 0;
+        const int rc = oge_bam_dup_sets_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, distance, &out, &h, &got);
+        if (rc) return rc;
+        if (got != n_lib) return -1;
+        s.assign(out, out + got);
+        hist.assign(h, h + 3 * OGE_DUP_SETS_BINS);
+        return 0;
+    }
     int coverage(int32_t binsize, const uint32_t **d_bins, uint64_t *nb, uint64_t *skipped, int32_t *overflow, int32_t *n_ref, const char **names,
                  const int32_t **lens) {
         if (!sam) {
@@ -2335,18 +2391,27 @@ int targets_bam_file(ChainContext &cc, const std::string &path, const std::strin
     return 0;
 }
 
-int dupmetrics_bam_file(ChainContext &cc, const std::string &path, const std::string &out, const std::string &command_line) {
+int dupmetrics_bam_file(ChainContext &cc, const std::string &path, const std::string &out, const std::string &command_line,
+                        int64_t optical_distance) {
     QcInput in(cc);
     if (in.load(path)) return -1;
     std::vector<OgeDupMetrics> m;
     std::vector<std::string> names;
     int unknown = 0;
-    const int rc = in.dup_metrics(m, names, &unknown);
+    int rc = in.dup_metrics(m, names, &unknown);
+    std::vector<OgeDupSetsLib> sets;
+    std::vector<uint64_t> hist;
+    const bool optical = optical_distance >= 0;
+    double metrics_ms = 0;
+    if (!rc && optical) {  // the same file once more: the duplicate sets of its records
+        oge_ctx_timing(cc.ctx, "dup_metrics", &metrics_ms);
+        rc = in.dup_sets(optical_distance, (int32_t)m.size(), sets, hist);
+    }
     in.z.buf.reset();
     if (rc) return cc.fail("dupmetrics");
     const auto t0 = clk();
     std::string text;
-    if (metrics_text(names, unknown, m, command_line, text)) {
+    if (metrics_text(names, unknown, m, command_line, text, optical ? &sets : nullptr, optical ? hist.data() : nullptr)) {
         fprintf(stderr, "openge: dupmetrics: %s\n", oge_last_error(nullptr));
         return -1;
     }
@@ -2359,7 +2424,15 @@ int dupmetrics_bam_file(ChainContext &cc, const std::string &path, const std::st
     } else if (write_text_file(out, std::vector<uint8_t>(text.begin(), text.end()))) {
         return -1;
     }
-    report_stages(cc, "dup_metrics", sec(t0, clk()));
+    report_stages(cc, optical ? "dup_sets" : "dup_metrics", sec(t0, clk()));
+    if (cc.verbose && optical) {
+        uint64_t tiers[3] = {0, 0, 0};
+        const char *nm[3] = {"dupsets_wave_sets", "dupsets_block_sets", "dupsets_host_sets"};
+        for (int k = 0; k < 3; ++k) oge_ctx_counter(cc.ctx, nm[k], &tiers[k]);
+        fprintf(stderr, "[openge] dupmetrics: dup_metrics %.1f ms; duplicate sets at optical distance %lld, sets of two or more pairs: "
+                        "%llu in a wave, %llu in a workgroup, %llu on the host\n",
+                metrics_ms, (long long)optical_distance, (unsigned long long)tiers[0], (unsigned long long)tiers[1], (unsigned long long)tiers[2]);
+    }
     return 0;
 }
 

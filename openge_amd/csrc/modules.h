@@ -22,6 +22,7 @@ namespace oge {
 
 // the struct by a name of its own: the plain name is the host-buffer entry point's
 using OgeDupMetrics = struct ::oge_dup_metrics;
+using OgeDupSetsLib = struct ::oge_dup_sets_lib;
 
 struct ChainContext;
 
@@ -231,6 +232,14 @@ public:
     std::vector<std::string> metricsLibraries;  // the ids' names, "" where no @RG names the id
     int metricsUnknown = 0;                     // the id of "Unknown Library"
     double metricsMs = 0;                       // stage dup_metrics, summed over the calls (ranks: the slowest)
+    // --optical-distance N (with --metrics; one GPU, records resident in HBM): the duplicate sets of the marked
+    // records (oge_dup_sets_dev), taken where the counts are taken in the in-place dedup and the fused sort; the file
+    // then carries the optical column and the set-size histogram (oge_dup_sets_text).  -1: not asked for.
+    int64_t opticalDistance = -1;
+    std::vector<OgeDupSetsLib> sets;            // by library id
+    std::vector<uint64_t> setsHist;             // 3 * OGE_DUP_SETS_BINS
+    double setsMs = 0;                          // stage dup_sets
+    uint64_t setsTiers[3] = {0, 0, 0};          // sets of two or more pairs counted in a wave, in a workgroup, on the host
     int writeMetrics() const;
 protected:
     int runInternal(ChainContext &cc, ReadBatch &b) override;
@@ -322,8 +331,10 @@ int targets_bam_file(ChainContext &cc, const std::string &path, const std::strin
 
 // `openge dupmetrics [-o out.txt] in.bam|in.sam`: the duplication metrics of a file that is already marked, by this
 // tool or another: the file into HBM through the same loader, one call (oge_bam_dup_metrics_dev, or
-// oge_dup_metrics_dev on the records of a SAM file), the text of oge_dup_metrics_text to out ("stdout": standard output)
-int dupmetrics_bam_file(ChainContext &cc, const std::string &path, const std::string &out, const std::string &command_line);
+// oge_dup_metrics_dev on the records of a SAM file), the text of oge_dup_metrics_text to out ("stdout": standard output).
+// optical_distance >= 0: also the duplicate sets (oge_bam_dup_sets_dev / oge_dup_sets_dev), the text of oge_dup_sets_text
+int dupmetrics_bam_file(ChainContext &cc, const std::string &path, const std::string &out, const std::string &command_line,
+                        int64_t optical_distance = -1);
 
 // `openge compare [-r REGION]... [-p] ref.bam other.bam [more...]` (commands/command_compare.cpp): every input
 // through a FileReader into its own batch in HBM, file 0 resident while the others come and go; the regions

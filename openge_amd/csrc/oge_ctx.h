@@ -13,6 +13,7 @@
 
 // the struct by a name of its own: the plain name is the host-buffer entry point's
 using OgeDupMetrics = struct oge_dup_metrics;
+using OgeDupSetsLib = struct oge_dup_sets_lib;
 
 struct OgeStageTimer {
     hipEvent_t start, stop;
@@ -87,6 +88,8 @@ struct oge_ctx {
     OgeContigTable targets_table{"tg_names", "tg_name_off", nullptr, "targets_table_uploads"};  // oge_targets_dev's
     std::vector<OgeDupMetrics> dm_out;  // what the last oge_bam_dup_metrics_dev call returned
     std::string dm_names;
+    std::vector<OgeDupSetsLib> ds_out;  // what the last oge_bam_dup_sets_dev call returned
+    std::vector<uint64_t> ds_hist;
     std::vector<uint8_t> sam_out_recs, sam_out_warn;
     std::vector<uint64_t> sam_out_off;
     std::map<std::string, uint64_t> counters;  // per call: work counts a stage reports (oge_ctx_counter)
@@ -245,6 +248,11 @@ int oge_targets_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off,
 // oge_dup_metrics_dev without the context checks and the timing reset (oge_bam_dup_metrics_dev calls it under its hold)
 int oge_dup_metrics_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_markdup_opts *opts, int32_t n_lib,
                          OgeDupMetrics *out);
+
+// ---- duplicate sets (dupsets.hip) ----
+// oge_dup_sets_dev without the context checks and the timing reset (oge_bam_dup_sets_dev calls it under its hold)
+int oge_dup_sets_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_markdup_opts *opts, int64_t distance,
+                      int32_t n_lib, OgeDupSetsLib *out_per_lib, uint64_t *hist);
 
 // ---- multi-GPU internals (dist.hip)
 oge_ctx *oge_comm_ctx(oge_comm *comm);

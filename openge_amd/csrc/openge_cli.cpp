@@ -19,7 +19,8 @@
 // section 25); `localrealign --auto-targets` computes the same intervals from the records it is handed.
 // `dedup --metrics FILE` and `mergesort -M --metrics FILE` also write Picard MarkDuplicates' metrics file, which the
 // reference never wrote (algorithms/mark_duplicates.cpp has no metrics code); `dupmetrics` writes it for a file that
-// is already marked (dupmetrics_bam_file, csrc/dupmetrics.hip).
+// is already marked (dupmetrics_bam_file, csrc/dupmetrics.hip).  --optical-distance N adds the
+// optical duplicates and the set-size histogram of the duplicate sets (csrc/dupsets.hip).
 //
 // Deliberate differences: view -B/-E cuts QUAL to the window of SEQ; the reference cuts the
 // qualities of the already shortened read a second time (algorithms/filter.cpp:188-189), which leaves fewer
@@ -43,6 +44,7 @@
 #include <sys/resource.h>
 #include <sys/time.h>
 
+#include <cerrno>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -73,9 +75,11 @@ const Opt kGlobal[] = {{"v", "verbose", false}, {"t", "threads", true}, {"d", "n
 const Opt kMergesort[] = {{"o", "out", true}, {"r", "region", true},  {"q", "mapq", true},
                           {"b", "byname", false}, {"n", "n", true}, {"C", "compresstempfiles", false},
                           {"M", "markduplicates", false}, {"R", "removeduplicates", false}, {"", "index", false},
-                          {"L", "regions", true}, {"", "noindex", false}, {"", "metrics", true}};
-const Opt kDedup[] = {{"o", "out", true}, {"r", "remove", false}, {"", "index", false}, {"", "metrics", true}};
-const Opt kDupmetrics[] = {{"o", "out", true}};
+                          {"L", "regions", true}, {"", "noindex", false}, {"", "metrics", true},
+                          {"", "optical-distance", true}};
+const Opt kDedup[] = {{"o", "out", true}, {"r", "remove", false}, {"", "index", false}, {"", "metrics", true},
+                      {"", "optical-distance", true}};
+const Opt kDupmetrics[] = {{"o", "out", true}, {"", "optical-distance", true}};
 const Opt kView[] = {{"o", "out", true}, {"n", "count", true}, {"q", "mapq", true}, {"l", "length", true},
                      {"B", "trimbegin", true}, {"E", "trimend", true}, {"r", "region", true}, {"L", "regions", true},
                      {"", "noindex", false}};
@@ -188,6 +192,13 @@ void usage_top() {
                     "    openge dupmetrics [-o out.txt] in.bam|in.sam\n"
                     "                                        the same metrics of a file that is already marked, by this tool or\n"
                     "                                        another (default: stdout); one file, one GPU, no stdin\n"
+                    "    --optical-distance N                with dedup --metrics, mergesort|sort -M|-R --metrics and dupmetrics:\n"
+                    "                                        the duplicate sets of the records, computed on the GPU: fills\n"
+                    "                                        READ_PAIR_OPTICAL_DUPLICATES (pairs of one set, read group and tile\n"
+                    "                                        within N pixels in x and y of one another, by the tile:x:y at the end\n"
+                    "                                        of 5- or 7-field read names; 100, or 2500 on patterned flow cells),\n"
+                    "                                        takes them out of ESTIMATED_LIBRARY_SIZE, and writes the set-size\n"
+                    "                                        histogram; one GPU, the records resident in HBM\n"
                     "\nGPU options (every command):\n"
                     "    --device N              first GPU\n"
                     "    --gpus G                ranks over G GPUs\n"
@@ -394,6 +405,30 @@ int main(int argc, const char **argv) {
             return -1;
         }
     }
+    int64_t optical_distance = -1;
+    if (p.count("optical-distance")) {  // refused before anything is read
+        const std::string v = p.get("optical-distance", "");
+        char *end = nullptr;
+        errno = 0;
+        const long long d = strtoll(v.c_str(), &end, 10);
+        if (v.empty() || v[0] < '0' || v[0] > '9' || *end || errno || d > INT32_MAX) {
+            fprintf(stderr, "openge %s: --optical-distance needs a number from 0 to 2147483647\n", cmd.c_str());
+            return -1;
+        }
+        if (cmd != "dupmetrics" && !p.count("metrics")) {
+            fprintf(stderr, "openge %s: --optical-distance needs --metrics (the optical duplicates go into the metrics file)\n", cmd.c_str());
+            return -1;
+        }
+        if (cc.gpus > 1) {
+            fprintf(stderr, "openge %s: --optical-distance is not provided with --gpus\n", cmd.c_str());
+            return -1;
+        }
+        if (split > 1 || compat) {
+            fprintf(stderr, "openge %s: --optical-distance is not provided with split chains or --compat-nonverbose-dedup\n", cmd.c_str());
+            return -1;
+        }
+        optical_distance = d;
+    }
     if (cmd == "localrealign" && p.count("auto-targets") && p.count("intervals")) {
         fprintf(stderr, "openge localrealign: -L and --auto-targets exclude each other\n");
         return -1;
@@ -441,7 +476,7 @@ int main(int argc, const char **argv) {
         return r;
     }
     if (cmd == "dupmetrics") {
-        const int r = dupmetrics_bam_file(cc, p.inputs[0], p.get("out", "stdout"), command_line);
+        const int r = dupmetrics_bam_file(cc, p.inputs[0], p.get("out", "stdout"), command_line, optical_distance);
         oge_ctx_destroy(cc.ctx);
         return r;
     }
@@ -502,6 +537,7 @@ int main(int argc, const char **argv) {
             md.splitChains = split;
             md.metricsFilename = p.get("metrics", "");
             md.metricsCommandLine = command_line;
+            md.opticalDistance = optical_distance;
             sorter.addSink(&md);
             md.addSink(&writer);
         } else {
@@ -516,6 +552,7 @@ int main(int argc, const char **argv) {
         md.splitChains = split;
         md.metricsFilename = p.get("metrics", "");
         md.metricsCommandLine = command_line;
+        md.opticalDistance = optical_distance;
         reader.addSink(&md);
         md.addSink(&writer);
         ret = writer.runChain(cc);

@@ -410,6 +410,34 @@ extern "C" int oge_bam_dup_metrics_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_
     return OGE_OK;
 }
 
+extern "C" int oge_bam_dup_sets_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, int64_t distance, const OgeDupSetsLib **out_per_lib,
+                                    const uint64_t **hist, int32_t *n_lib) {
+    if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
+    if (!out_per_lib || !hist || !n_lib || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
+    OgeCall call(ctx, /*hold=*/true);
+    *out_per_lib = nullptr;
+    *hist = nullptr;
+    *n_lib = 0;
+    uint8_t *X;
+    uint64_t *xoff, n;
+    BamFile f;
+    int rc = decode_for_qc(ctx, d_z, zbytes, &X, &xoff, &n, &f);
+    if (rc) return rc;
+    oge_mergesort_opts mo;
+    oge_mergesort_opts_init(&mo);
+    const LibTable lt(f.header, (int32_t)f.ref_names.size(), &mo);
+    int16_t top = lt.o.unknown_lib;
+    for (size_t g = 0; g < f.header.rg.size(); ++g) top = std::max(top, lt.libs[g]);
+    ctx->ds_out.assign((size_t)top + 1, OgeDupSetsLib{});
+    ctx->ds_hist.assign(3 * OGE_DUP_SETS_BINS, 0);
+    rc = oge_dup_sets_impl(ctx, X, xoff, n, &lt.o, distance, (int32_t)top + 1, ctx->ds_out.data(), ctx->ds_hist.data());
+    if (rc) return rc;
+    *out_per_lib = ctx->ds_out.data();
+    *hist = ctx->ds_hist.data();
+    *n_lib = (int32_t)top + 1;
+    return OGE_OK;
+}
+
 extern "C" int oge_bam_count_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, uint64_t *n_reads) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
     if (!n_reads || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");

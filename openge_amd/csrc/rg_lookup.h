@@ -1,6 +1,6 @@
 // rg_lookup.h -- the library of a record on the device: the RG tag found as the input pass of records.hip finds it
 // (FindTag semantics, util/bamtools/BamAlignment.cpp:270-294,699-780) and looked up in the uploaded read-group
-// table.  Used by dupmetrics.hip.  The input pass keeps its own copy: there the walk reads through the LDS tile or
+// table.  Used by dupmetrics.hip and dupsets.hip.  The input pass keeps its own copy: there the walk reads through the LDS tile or
 // global memory by a reader type and feeds the pair hash from the words it loads, and replacing it with this
 // function changes the registers k_input_pass uses, on the benchmark's headline path.
 #pragma once
@@ -18,7 +18,10 @@
 //           there), and when the next tag would start at or past the record's end or with a NUL.
 //   lookup  a non-empty value equal to the id of group g gives rg.lib[g] (the first such g); no tag, an empty value
 //           or an unlisted one gives rg.unknown_lib.
-__device__ __forceinline__ int32_t oge_rg_library(const uint8_t *__restrict__ r, uint32_t bs, const OgeRgTable &rg) {
+//
+// oge_rg_index gives the index g itself, or -1 without a listed value (dupsets.hip: two pairs are optical
+// duplicates of one another only within one read group); oge_rg_library is rg.lib of it.
+__device__ __forceinline__ int32_t oge_rg_index(const uint8_t *__restrict__ r, uint32_t bs, const OgeRgTable &rg) {
     const uint32_t w3 = oge_ldu32(r + OGE_OFF_LNAME), w4 = oge_ldu32(r + OGE_OFF_NCIGAR);
     const uint64_t lname = w3 & 0xFF, nc = w4 & 0xFFFF, lseq = oge_ldu32(r + OGE_OFF_LSEQ);
     const uint64_t tend = 4ull + bs;
@@ -60,7 +63,7 @@ __device__ __forceinline__ int32_t oge_rg_library(const uint8_t *__restrict__ r,
         }
         if (!ok || p >= tend || r[p] == 0) break;
     }
-    if (!rgl) return rg.unknown_lib;
+    if (!rgl) return -1;
     // a value of <= 15 bytes as four zero-padded words, compared with the table's idw
     uint32_t rv[4] = {0u, 0u, 0u, 0u};
     if (rgl <= 15) {
@@ -87,7 +90,12 @@ __device__ __forceinline__ int32_t oge_rg_library(const uint8_t *__restrict__ r,
         } else {
             for (uint32_t y = 0; y < Lg && eq; ++y) eq = rg.ids[o + y] == r[rgv + y];
         }
-        if (eq) return rg.lib[g];
+        if (eq) return g;
     }
-    return rg.unknown_lib;
+    return -1;
+}
+
+__device__ __forceinline__ int32_t oge_rg_library(const uint8_t *__restrict__ r, uint32_t bs, const OgeRgTable &rg) {
+    const int32_t g = oge_rg_index(r, bs, rg);
+    return g < 0 ? rg.unknown_lib : rg.lib[g];
 }

@@ -386,6 +386,10 @@ def lib() -> C.CDLL:
         "oge_bam_dup_metrics_dev": (C.c_int, [vp, vp, u64, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(u64), C.POINTER(i32)]),
         "oge_estimate_library_size": (C.c_int, [u64, u64, C.POINTER(u64)]),
         "oge_dup_metrics_text": (C.c_int, [vp, vp, i32, C.c_char_p, vp, u64, C.POINTER(u64)]),
+        "oge_dup_sets_dev": (C.c_int, [vp, vp, vp, u64, vp, C.c_int64, i32, vp, vp]),
+        "oge_dup_sets": (C.c_int, [vp, vp, u64, vp, u64, vp, C.c_int64, i32, vp, vp]),
+        "oge_bam_dup_sets_dev": (C.c_int, [vp, vp, u64, C.c_int64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]),
+        "oge_dup_sets_text": (C.c_int, [vp, vp, vp, i32, vp, C.c_char_p, vp, u64, C.POINTER(u64)]),
         "oge_bam_stats_dev": (C.c_int, [vp, vp, u64, u32, vp, C.POINTER(vp), C.POINTER(vp)]),
         "oge_bam_coverage_dev": (C.c_int, [vp, vp, u64, i32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]),
         "oge_bam_count_dev": (C.c_int, [vp, vp, u64, C.POINTER(u64)]),
@@ -459,6 +463,25 @@ def dup_metrics_text(rows, command_line: str, cap: int | None = None) -> bytes:
     buf = C.create_string_buffer(max(cap, 1))
     check(lib().oge_dup_metrics_text(arr, _ptr(m), len(rows), command_line.encode(), buf, cap, C.byref(need)))
     return buf.raw[:min(max(cap, 1) - 1, need.value)]
+
+
+DUP_SETS_BINS = 1024  # OGE_DUP_SETS_BINS
+
+
+def dup_sets_text(rows, hist, command_line: str) -> bytes:
+    """oge_dup_sets_text (host only): rows = [(library name, the six counters of oge_dup_metrics, the four of
+    oge_dup_sets_lib)], hist = the three histogram columns (3, DUP_SETS_BINS) -> the metrics file with the optical
+    column and the set-size histogram."""
+    names = [nm.encode() if isinstance(nm, str) else bytes(nm) for nm, _, _ in rows]
+    arr = (C.c_char_p * max(len(rows), 1))(*names)
+    m = np.array([list(c6) for _, c6, _ in rows] or [[0] * 6], dtype=np.uint64)
+    s4 = np.array([list(c4) for _, _, c4 in rows] or [[0] * 4], dtype=np.uint64)
+    h = np.ascontiguousarray(hist, dtype=np.uint64).reshape(3 * DUP_SETS_BINS)
+    need = C.c_uint64()
+    check(lib().oge_dup_sets_text(arr, _ptr(m), _ptr(s4), len(rows), _ptr(h), command_line.encode(), None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value + 1)
+    check(lib().oge_dup_sets_text(arr, _ptr(m), _ptr(s4), len(rows), _ptr(h), command_line.encode(), buf, need.value + 1, C.byref(need)))
+    return buf.raw[:need.value]
 
 
 def exported_symbols() -> list[str]:
@@ -908,6 +931,33 @@ class Context:
             out = np.frombuffer(C.string_at(po.value, 48 * n.value), np.uint64).reshape(n.value, 6).copy()
             names = C.string_at(pn.value, nb.value).split(b"\0")[:n.value]
             return out, [x.decode() for x in names], unk.value
+        return self._with_file(data, run)
+
+    # ---- duplicate sets: optical duplicates and set-size histograms (csrc/dupsets.hip)
+    def dup_sets_dev(self, d_recs, d_off, n: int, opts: MarkdupOpts, distance: int, n_lib: int) -> tuple[np.ndarray, np.ndarray]:
+        """oge_dup_sets_dev on device records -> (uint64 (n_lib, 4): pairs, sets, located, optical by library id,
+        uint64 (3, DUP_SETS_BINS): all_sets, optical_sets, non_optical_sets)."""
+        out = np.full((max(n_lib, 1), 4), 0xDEADBEEF, np.uint64)  # the call sets both
+        hist = np.full((3, DUP_SETS_BINS), 0xDEADBEEF, np.uint64)
+        check(lib().oge_dup_sets_dev(self.h, d_recs, d_off, n, C.byref(opts), distance, n_lib, _ptr(out), _ptr(hist)), self.h)
+        return out[:n_lib], hist
+
+    def dup_sets(self, recs: np.ndarray, offs: np.ndarray, n: int, opts: MarkdupOpts, distance: int, n_lib: int) -> tuple[np.ndarray, np.ndarray]:
+        """oge_dup_sets: the same from host buffers (recs with 16 bytes of slack behind the last record)."""
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        out = np.full((max(n_lib, 1), 4), 0xDEADBEEF, np.uint64)
+        hist = np.full((3, DUP_SETS_BINS), 0xDEADBEEF, np.uint64)
+        check(lib().oge_dup_sets(self.h, _ptr(recs), max(recs.nbytes - 16, 0), _ptr(offs), n, C.byref(opts), distance, n_lib, _ptr(out), _ptr(hist)), self.h)
+        return out[:n_lib], hist
+
+    def bam_dup_sets(self, data: bytes, distance: int) -> tuple[np.ndarray, np.ndarray]:
+        """oge_bam_dup_sets_dev on a copy of a whole BAM file in HBM: the libraries numbered from its own header."""
+        def run(dz, nbytes):
+            po, ph, n = C.c_void_p(), C.c_void_p(), C.c_int32()
+            check(lib().oge_bam_dup_sets_dev(self.h, dz, nbytes, distance, C.byref(po), C.byref(ph), C.byref(n)), self.h)
+            out = np.frombuffer(C.string_at(po.value, 32 * n.value), np.uint64).reshape(n.value, 4).copy()
+            hist = np.frombuffer(C.string_at(ph.value, 24 * DUP_SETS_BINS), np.uint64).reshape(3, DUP_SETS_BINS).copy()
+            return out, hist
         return self._with_file(data, run)
 
     # ---- SAM / FASTQ text (csrc/sam.hip)
