@@ -1,5 +1,6 @@
 // bamio.cpp -- host BGZF/BAM codec (see bamio.h for the reference interfaces replaced).
 #include "bamio.h"
+#include "lib_table.h"
 
 #include <dlfcn.h>
 #include <zlib.h>
@@ -12,6 +13,7 @@
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <cstring>
+#include <map>
 #include <sstream>
 #include <thread>
 
@@ -475,6 +477,41 @@ std::string BamHeaderModel::to_string() const {
     }
     for (auto &c : co) s << "@CO\t" << c << "\n";
     return s.str();
+}
+
+// ---------------- read-group -> library table (lib_table.h) ----------------
+LibTable::LibTable(const BamHeaderModel &h) : n_rg((int32_t)h.rg.size()) {
+    static const std::string kUnknown = "Unknown Library";
+    std::map<std::string, int16_t> lib_ids;
+    int16_t next = 1;
+    for (auto &rg : h.rg) {
+        const std::string &lib = rg.lb.empty() ? kUnknown : rg.lb;
+        auto it = lib_ids.find(lib);
+        if (it == lib_ids.end()) it = lib_ids.emplace(lib, next++).first;
+        rg_lib.push_back(it->second);
+        ids += rg.id;
+        ids.push_back('\0');
+    }
+    const auto unk = lib_ids.find(kUnknown);
+    unknown_lib = unk != lib_ids.end() ? unk->second : next;
+    n_lib = 1 + (int32_t)std::max(unknown_lib, rg_lib.empty() ? unknown_lib : *std::max_element(rg_lib.begin(), rg_lib.end()));
+    names.assign((size_t)n_lib, std::string());
+    for (auto &kv : lib_ids) names[kv.second] = kv.first;
+    rg_lib.push_back(0);
+}
+
+oge_markdup_opts LibTable::opts(int32_t n_ref, int compat_nonverbose_index, int split_chains) const {
+    oge_markdup_opts o;
+    memset(&o, 0, sizeof o);
+    o.n_ref = n_ref;
+    o.rg_ids = ids.c_str();
+    o.rg_ids_bytes = ids.size();
+    o.rg_lib = rg_lib.data();
+    o.n_rg = n_rg;
+    o.unknown_lib = unknown_lib;
+    o.compat_nonverbose_index = compat_nonverbose_index;
+    o.split_chains = split_chains;
+    return o;
 }
 
 // ---------------- BAM ----------------

@@ -81,8 +81,7 @@ struct BamHeaderModel {
     std::vector<std::string> co;
     bool parse(const std::string &text, std::string &err);
     std::string to_string() const;
-    // Library id per read group in the order MarkDuplicates would discover them does not
-    // matter; ids here: 1 + index of the distinct LB name, "Unknown Library" last.
+    // The library ids of the read groups are LibTable's (lib_table.h).
 };
 
 // FileWriter's @PG line (algorithms/file_writer.cpp:76-89): ID openge, or openge-k when taken,

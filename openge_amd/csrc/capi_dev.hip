@@ -12,24 +12,6 @@
 #include <cstring>
 #include <string>
 
-// implemented in sort.hip / markdup.hip
-int oge_sort_buffers(oge_ctx *ctx, uint64_t n, uint64_t **keys, uint32_t **vals);
-unsigned int *oge_sort_counts(oge_ctx *ctx);
-int oge_sort_keys_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref,
-                      bool keys_ready, uint64_t **kout, uint32_t **vout, const RecMeta *meta_in = nullptr,
-                      RecMeta *meta_out = nullptr);
-int oge_markdup_prepare(oge_ctx *ctx, const oge_markdup_opts *opts, uint64_t n, const char *name, RecMeta **meta,
-                        OgeRgTable *rg);
-int oge_markdup_finish(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_markdup_opts *opts,
-                       const RecMeta *meta, uint8_t *d_dup, int apply, uint64_t *n_dup_out, uint64_t *d_desc, bool *desc_ok,
-                       const uint64_t *skeys);
-int oge_meta_gather(oge_ctx *ctx, const RecMeta *in, const uint32_t *perm, uint64_t n, RecMeta *out);
-int oge_sort_keys_dev_hook(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref,
-                           bool keys_ready, uint64_t **kout, uint32_t **vout, const RecMeta *meta_in, RecMeta *meta_out,
-                           const OgeSortGatherHook *hook);
-int oge_markdup_run(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_markdup_opts *opts,
-                    uint8_t *d_dup, int apply, uint64_t *n_dup_out);
-
 static thread_local std::string g_last_error;
 
 int oge_fail(oge_ctx *ctx, int code, const char *msg) {

@@ -30,13 +30,6 @@
 #include <string>
 #include <vector>
 
-int oge_markdup_prepare(oge_ctx *ctx, const oge_markdup_opts *opts, uint64_t n, const char *name, RecMeta **meta,
-                        OgeRgTable *rg);
-int oge_sort_buffers(oge_ctx *ctx, uint64_t n, uint64_t **keys, uint32_t **vals);
-unsigned int *oge_sort_counts(oge_ctx *ctx);
-int oge_sort_keys_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref,
-                      bool keys_ready, uint64_t **kout, uint32_t **vout, const RecMeta *meta_in, RecMeta *meta_out);
-
 namespace {
 
 constexpr int kT = 256;

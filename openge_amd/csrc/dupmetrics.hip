@@ -99,60 +99,21 @@ __global__ __launch_bounds__(kT) void k_dm_count(const uint8_t *__restrict__ rec
     }
 }
 
-// The read-group table on the device, as oge_markdup_prepare uploads it (in workspaces of its own: a dedup in
-// flight keeps its table).
-int upload_rg_table(oge_ctx *ctx, const oge_markdup_opts *opts, OgeRgTable *rg) {
-    std::vector<uint32_t> offs(opts->n_rg + 1, 0);
-    const char *p = opts->rg_ids;
-    for (int32_t g = 0; g < opts->n_rg; ++g) {
-        const size_t left = opts->rg_ids_bytes - (size_t)(p - opts->rg_ids);
-        const size_t L = strnlen(p, left);
-        if (L == left) return oge_fail(ctx, OGE_ERR_ARG, "dup_metrics: the read-group ids are not n_rg NUL-terminated strings");
-        offs[g + 1] = offs[g] + (uint32_t)L + 1;
-        p += L + 1;
-    }
-    std::vector<uint8_t> w16((size_t)opts->n_rg * 16, 0);  // idw: ids of <= 15 bytes, zero-padded
-    for (int32_t g = 0; g < opts->n_rg; ++g)
-        if (offs[g + 1] - offs[g] - 1 <= 15) memcpy(&w16[(size_t)g * 16], opts->rg_ids + offs[g], offs[g + 1] - offs[g] - 1);
-    uint8_t *ids = (uint8_t *)ctx->ws("dm_rgids", offs.back() + 16);
-    uint4 *idw = (uint4 *)ctx->ws("dm_rgidw", w16.size() + 16);
-    uint32_t *doff = (uint32_t *)ctx->ws("dm_rgoff", offs.size() * 4);
-    int16_t *lib = (int16_t *)ctx->ws("dm_rglib", (size_t)(opts->n_rg + 1) * 2);
-    if (!ids || !idw || !doff || !lib) return OGE_ERR_HIP;
-    if (offs.back()) OGE_HIP_TRY(ctx, hipMemcpyAsync(ids, opts->rg_ids, offs.back(), hipMemcpyHostToDevice, ctx->stream));
-    if (!w16.empty()) OGE_HIP_TRY(ctx, hipMemcpyAsync(idw, w16.data(), w16.size(), hipMemcpyHostToDevice, ctx->stream));
-    OGE_HIP_TRY(ctx, hipMemcpyAsync(doff, offs.data(), offs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (opts->n_rg) OGE_HIP_TRY(ctx, hipMemcpyAsync(lib, opts->rg_lib, (size_t)opts->n_rg * 2, hipMemcpyHostToDevice, ctx->stream));
-    rg->ids = ids;
-    rg->idw = idw;
-    rg->off = doff;
-    rg->lib = lib;
-    rg->n_rg = opts->n_rg;
-    rg->unknown_lib = opts->unknown_lib;
-    rg->split_k = 0;
-    // the host copies above read pageable memory; make sure they are done before the vectors go
-    OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return OGE_OK;
-}
-
 }  // namespace
 
 int oge_dup_metrics_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_markdup_opts *opts, int32_t n_lib,
                          OgeDupMetrics *out) {
     if (n_lib < 1 || n_lib > 32768) return oge_fail(ctx, OGE_ERR_ARG, "dup_metrics: n_lib out of [1, 32768]");
-    if (opts->n_rg < 0 || (opts->n_rg && (!opts->rg_ids || !opts->rg_lib))) return oge_fail(ctx, OGE_ERR_ARG, "dup_metrics: bad read-group table");
-    if (opts->n_rg > OGE_MAX_RG) return oge_fail(ctx, OGE_ERR_LIMIT, "dup_metrics: more than 32767 read groups");
     if (n && (!d_recs || !d_off)) return oge_fail(ctx, OGE_ERR_ARG, "dup_metrics: null argument");
-    if (opts->unknown_lib < 0 || opts->unknown_lib >= n_lib) return oge_fail(ctx, OGE_ERR_ARG, "dup_metrics: unknown_lib outside [0, n_lib)");
-    for (int32_t g = 0; g < opts->n_rg; ++g)
-        if (opts->rg_lib[g] < 0 || opts->rg_lib[g] >= n_lib)
-            return oge_fail(ctx, OGE_ERR_ARG, ("dup_metrics: the library id of read group " + std::to_string(g) + " is outside [0, n_lib)").c_str());
+    int rc = oge_rg_table_check(ctx, opts, "dup_metrics", n_lib);
+    if (rc) return rc;
     memset(out, 0, (size_t)n_lib * sizeof *out);
     ctx->counters["dupmetrics_tile_records"] = kTile;
     ctx->counters["dupmetrics_lds_libs"] = kLdsLibs;
+    // the table in workspaces of its own: a dedup in flight keeps its table
     OgeRgTable rg;
-    int rc = upload_rg_table(ctx, opts, &rg);
-    if (rc) return rc;
+    if ((rc = oge_rg_table_upload(ctx, opts, "dm", &rg))) return rc;
+    rg.split_k = 0;
     const uint32_t n_keys = (uint32_t)n_lib * kNC;
     unsigned long long *tab = (unsigned long long *)ctx->ws("dm_table", (size_t)n_keys * 8);
     if (!tab) return OGE_ERR_HIP;

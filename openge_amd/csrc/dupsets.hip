@@ -32,8 +32,6 @@
 #include "records.h"
 #include "rg_lookup.h"
 
-int oge_markdup_prepare(oge_ctx *ctx, const oge_markdup_opts *opts, uint64_t n, const char *name, RecMeta **meta, OgeRgTable *rg);
-
 namespace {
 
 constexpr int kT = 256;
@@ -399,22 +397,9 @@ int oge_dup_sets_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off
     if (distance < 0 || distance > 0x7fffffffll) return oge_fail(ctx, OGE_ERR_ARG, "dup_sets: distance outside [0, 2^31 - 1]");
     if (n >= (1ull << 31)) return oge_fail(ctx, OGE_ERR_LIMIT, "dup_sets: 2^31 records or more");
     if (n && (!d_recs || !d_off)) return oge_fail(ctx, OGE_ERR_ARG, "dup_sets: null argument");
-    if (opts_in->n_rg < 0 || (opts_in->n_rg && (!opts_in->rg_ids || !opts_in->rg_lib))) return oge_fail(ctx, OGE_ERR_ARG, "dup_sets: bad read-group table");
+    if (int rc = oge_rg_table_check(ctx, opts_in, "dup_sets", n_lib)) return rc;
     if (opts_in->split_chains > 1 || opts_in->compat_nonverbose_index)
         return oge_fail(ctx, OGE_ERR_ARG, "dup_sets: split chains and the non-verbose index are not supported");
-    if (opts_in->unknown_lib < 0 || opts_in->unknown_lib >= n_lib) return oge_fail(ctx, OGE_ERR_ARG, "dup_sets: unknown_lib outside [0, n_lib)");
-    for (int32_t g = 0; g < opts_in->n_rg; ++g)
-        if (opts_in->rg_lib[g] < 0 || opts_in->rg_lib[g] >= n_lib)
-            return oge_fail(ctx, OGE_ERR_ARG, ("dup_sets: the library id of read group " + std::to_string(g) + " is outside [0, n_lib)").c_str());
-    {  // the ids must be n_rg NUL-terminated strings (oge_markdup_prepare reads them as such)
-        const char *p = opts_in->rg_ids;
-        for (int32_t g = 0; g < opts_in->n_rg; ++g) {
-            const size_t left = opts_in->rg_ids_bytes - (size_t)(p - opts_in->rg_ids);
-            const size_t L = strnlen(p, left);
-            if (L == left) return oge_fail(ctx, OGE_ERR_ARG, "dup_sets: the read-group ids are not n_rg NUL-terminated strings");
-            p += L + 1;
-        }
-    }
     oge_markdup_opts o = *opts_in;  // the plain stages: no test knobs
     o.debug_sort_groups = 0;
     o.debug_hash_bits = 0;

@@ -2,6 +2,7 @@
 #include "../../include/openge_hip.h"
 #include "bamio.h"
 #include "capi_common.h"
+#include "lib_table.h"
 #include "synth.h"
 
 #include <algorithm>
@@ -11,7 +12,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <thread>
 #include <vector>
@@ -122,33 +122,15 @@ int oge_bam_header_text(const oge_bam *b, char *buf, uint64_t cap, uint64_t *len
 }
 
 int oge_bam_markdup_opts(const oge_bam *b, oge_markdup_opts *opts, char **rg_ids_buf, int16_t **rg_lib_buf) {
-    // Library naming follows getLibraryName (algorithms/mark_duplicates.cpp:301-318): the LB of
-    // the record's @RG if present and non-empty, else "Unknown Library".  Distinct names get
-    // distinct ids; which id a name gets does not change any duplicate decision.
-    const auto &rgs = b->f.header.rg;
-    std::map<std::string, int16_t> lib_ids;
-    std::string ids;
-    int16_t *libs = (int16_t *)malloc(sizeof(int16_t) * std::max<size_t>(1, rgs.size()));
-    int16_t next = 1;
-    for (size_t i = 0; i < rgs.size(); ++i) {
-        std::string lib = rgs[i].lb.empty() ? std::string("Unknown Library") : rgs[i].lb;
-        auto it = lib_ids.find(lib);
-        if (it == lib_ids.end()) it = lib_ids.emplace(lib, next++).first;
-        libs[i] = it->second;
-        ids += rgs[i].id;
-        ids.push_back('\0');
-    }
-    auto unk = lib_ids.find("Unknown Library");
-    int16_t unknown = unk != lib_ids.end() ? unk->second : next++;
-    char *idbuf = (char *)malloc(std::max<size_t>(1, ids.size()));
-    memcpy(idbuf, ids.data(), ids.size());
-    memset(opts, 0, sizeof(*opts));
-    opts->n_ref = (int32_t)b->f.ref_names.size();
+    // the header's table (lib_table.h) in malloc'd copies that the caller frees
+    const LibTable lt(b->f.header);
+    char *idbuf = (char *)malloc(lt.ids.size() + 1);
+    int16_t *libs = (int16_t *)malloc(sizeof(int16_t) * lt.rg_lib.size());
+    memcpy(idbuf, lt.ids.c_str(), lt.ids.size() + 1);
+    memcpy(libs, lt.rg_lib.data(), sizeof(int16_t) * lt.rg_lib.size());
+    *opts = lt.opts((int32_t)b->f.ref_names.size());
     opts->rg_ids = idbuf;
-    opts->rg_ids_bytes = ids.size();
     opts->rg_lib = libs;
-    opts->n_rg = (int32_t)rgs.size();
-    opts->unknown_lib = unknown;
     *rg_ids_buf = idbuf;
     *rg_lib_buf = libs;
     return OGE_OK;

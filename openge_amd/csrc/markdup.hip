@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 namespace {
@@ -1023,7 +1024,52 @@ static int md_layout(oge_ctx *ctx, const oge_markdup_opts *opts, KeyLayout *L) {
     return OGE_OK;
 }
 
-// Allocate the per-record ReadEnds summaries (`name` selects the buffer) and upload the RG table.
+int oge_rg_table_check(oge_ctx *ctx, const oge_markdup_opts *opts, const char *who, int32_t n_lib) {
+    auto fail = [&](int code, const std::string &what) { return oge_fail(ctx, code, (std::string(who) + ": " + what).c_str()); };
+    if (opts->n_rg < 0 || (opts->n_rg && (!opts->rg_ids || !opts->rg_lib))) return fail(OGE_ERR_ARG, "bad read-group table");
+    if (opts->n_rg > OGE_MAX_RG) return fail(OGE_ERR_LIMIT, "more than 32767 read groups");
+    if (n_lib) {
+        if (opts->unknown_lib < 0 || opts->unknown_lib >= n_lib) return fail(OGE_ERR_ARG, "unknown_lib outside [0, n_lib)");
+        for (int32_t g = 0; g < opts->n_rg; ++g)
+            if (opts->rg_lib[g] < 0 || opts->rg_lib[g] >= n_lib)
+                return fail(OGE_ERR_ARG, "the library id of read group " + std::to_string(g) + " is outside [0, n_lib)");
+    } else {
+        bool negative = opts->unknown_lib < 0;
+        for (int32_t g = 0; g < opts->n_rg; ++g) negative |= opts->rg_lib[g] < 0;
+        if (negative) return fail(OGE_ERR_ARG, "negative library id");
+    }
+    const char *p = opts->rg_ids;
+    for (int32_t g = 0; g < opts->n_rg; ++g) {  // the upload reads exactly the bytes this walk has seen
+        const size_t left = opts->rg_ids_bytes - (size_t)(p - opts->rg_ids);
+        const size_t L = strnlen(p, left);
+        if (L == left) return fail(OGE_ERR_ARG, "the read-group ids are not n_rg NUL-terminated strings");
+        p += L + 1;
+    }
+    return OGE_OK;
+}
+
+int oge_rg_table_upload(oge_ctx *ctx, const oge_markdup_opts *opts, const char *ws, OgeRgTable *rg) {
+    std::vector<uint32_t> offs(opts->n_rg + 1, 0);
+    for (int32_t g = 0; g < opts->n_rg; ++g) offs[g + 1] = offs[g] + (uint32_t)strlen(opts->rg_ids + offs[g]) + 1;
+    std::vector<uint8_t> w16((size_t)opts->n_rg * 16, 0);  // idw: ids of <= 15 bytes, zero-padded
+    for (int32_t g = 0; g < opts->n_rg; ++g)
+        if (offs[g + 1] - offs[g] - 1 <= 15) memcpy(&w16[(size_t)g * 16], opts->rg_ids + offs[g], offs[g + 1] - offs[g] - 1);
+    const std::string pre(ws);
+    uint8_t *ids = (uint8_t *)ctx->ws((pre + "_rgids").c_str(), offs.back() + 16);
+    uint4 *idw = (uint4 *)ctx->ws((pre + "_rgidw").c_str(), w16.size() + 16);
+    uint32_t *doff = (uint32_t *)ctx->ws((pre + "_rgoff").c_str(), offs.size() * 4);
+    int16_t *lib = (int16_t *)ctx->ws((pre + "_rglib").c_str(), (size_t)(opts->n_rg + 1) * 2);
+    if (!ids || !idw || !doff || !lib) return OGE_ERR_HIP;
+    if (offs.back()) OGE_HIP_TRY(ctx, hipMemcpyAsync(ids, opts->rg_ids, offs.back(), hipMemcpyHostToDevice, ctx->stream));
+    if (!w16.empty()) OGE_HIP_TRY(ctx, hipMemcpyAsync(idw, w16.data(), w16.size(), hipMemcpyHostToDevice, ctx->stream));
+    OGE_HIP_TRY(ctx, hipMemcpyAsync(doff, offs.data(), offs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (opts->n_rg) OGE_HIP_TRY(ctx, hipMemcpyAsync(lib, opts->rg_lib, (size_t)opts->n_rg * 2, hipMemcpyHostToDevice, ctx->stream));
+    *rg = OgeRgTable{ids, idw, doff, lib, opts->n_rg, opts->unknown_lib, opts->split_chains};
+    // the host copies above read pageable memory; make sure they are done before the vectors go
+    OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return OGE_OK;
+}
+
 int oge_markdup_prepare(oge_ctx *ctx, const oge_markdup_opts *opts, uint64_t n, const char *name, RecMeta **meta,
                         OgeRgTable *rg) {
     if (!opts) return oge_fail(ctx, OGE_ERR_ARG, "markdup: opts is NULL");
@@ -1032,44 +1078,15 @@ int oge_markdup_prepare(oge_ctx *ctx, const oge_markdup_opts *opts, uint64_t n, 
     if (opts->split_chains > 1 && opts->compat_nonverbose_index)
         return oge_fail(ctx, OGE_ERR_ARG, "markdup: split_chains > 1 with compat_nonverbose_index is not supported");
     if (n > 0xFFFFFFFEull) return oge_fail(ctx, OGE_ERR_LIMIT, "markdup: more than 2^32-2 records");
-    if (opts->n_rg < 0 || (opts->n_rg && (!opts->rg_ids || !opts->rg_lib)))
-        return oge_fail(ctx, OGE_ERR_ARG, "markdup: bad read-group table");
-    if (opts->n_rg > OGE_MAX_RG) return oge_fail(ctx, OGE_ERR_LIMIT, "markdup: more than 32767 read groups");
+    if (int rc = oge_rg_table_check(ctx, opts, "markdup", 0)) return rc;
     // refuse a layout the group keys cannot hold here, before any pass has written a buffer of the caller's
     // (the fused chain's output arena is lent out as scratch, and its stages check the layout only later)
     KeyLayout L0;
     if (int lrc = md_layout(ctx, opts, &L0)) return lrc;
     *meta = (RecMeta *)(strcmp(name, "md_meta_in") ? ctx->ws(name, (n + 1) * sizeof(RecMeta))
                                                    : ctx->scratch(name, (n + 1) * sizeof(RecMeta)));
-    std::vector<uint32_t> offs(opts->n_rg + 1, 0);
-    const char *p = opts->rg_ids;
-    for (int32_t g = 0; g < opts->n_rg; ++g) {
-        size_t L = strnlen(p, opts->rg_ids_bytes - (size_t)(p - opts->rg_ids));
-        offs[g + 1] = offs[g] + (uint32_t)L + 1;
-        p += L + 1;
-    }
-    std::vector<uint8_t> w16((size_t)opts->n_rg * 16, 0);  // idw: ids of <= 15 bytes, zero-padded
-    for (int32_t g = 0; g < opts->n_rg; ++g)
-        if (offs[g + 1] - offs[g] - 1 <= 15) memcpy(&w16[(size_t)g * 16], opts->rg_ids + offs[g], offs[g + 1] - offs[g] - 1);
-    uint8_t *ids = (uint8_t *)ctx->ws("md_rgids", offs.back() + 16);
-    uint4 *idw = (uint4 *)ctx->ws("md_rgidw", w16.size() + 16);
-    uint32_t *doff = (uint32_t *)ctx->ws("md_rgoff", offs.size() * 4);
-    int16_t *lib = (int16_t *)ctx->ws("md_rglib", (size_t)(opts->n_rg + 1) * 2);
-    if (!*meta || !ids || !idw || !doff || !lib) return OGE_ERR_HIP;
-    if (offs.back()) OGE_HIP_TRY(ctx, hipMemcpyAsync(ids, opts->rg_ids, offs.back(), hipMemcpyHostToDevice, ctx->stream));
-    if (!w16.empty()) OGE_HIP_TRY(ctx, hipMemcpyAsync(idw, w16.data(), w16.size(), hipMemcpyHostToDevice, ctx->stream));
-    OGE_HIP_TRY(ctx, hipMemcpyAsync(doff, offs.data(), offs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (opts->n_rg) OGE_HIP_TRY(ctx, hipMemcpyAsync(lib, opts->rg_lib, (size_t)opts->n_rg * 2, hipMemcpyHostToDevice, ctx->stream));
-    rg->ids = ids;
-    rg->idw = idw;
-    rg->off = doff;
-    rg->lib = lib;
-    rg->n_rg = opts->n_rg;
-    rg->unknown_lib = opts->unknown_lib;
-    rg->split_k = opts->split_chains;
-    // the host copies above read pageable memory; make sure they are done before returning
-    OGE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return OGE_OK;
+    if (!*meta) return OGE_ERR_HIP;
+    return oge_rg_table_upload(ctx, opts, "md", rg);
 }
 
 namespace {
@@ -1619,9 +1636,6 @@ int oge_md_apply_inplace(oge_ctx *ctx, uint8_t *recs, const uint64_t *off, uint6
 // (record index = i); its bytes are at recs + meta[i].src (only read to confirm pair keys).
 // dup[i] receives 1/0/2 (see oge_markdup); with apply, FLAG 0x400 is rewritten in place at
 // recs + off[i].
-int oge_markdup_finish_pre(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_markdup_opts *opts,
-                           const RecMeta *meta, uint8_t *d_dup, int apply, uint64_t *n_dup_out, uint64_t *d_desc, bool *desc_ok,
-                           const uint64_t *skeys, const OgeMdFrags *pre);
 int oge_markdup_finish(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off, uint64_t n,
                        const oge_markdup_opts *opts, const RecMeta *meta, uint8_t *d_dup, int apply, uint64_t *n_dup_out,
                        uint64_t *d_desc, bool *desc_ok, const uint64_t *skeys) {

@@ -42,6 +42,18 @@ struct OgeMdPairs {  // pair ReadEnds, np entries (see k_pair_build for the pack
     uint32_t np = 0;
 };
 
+// The options checked (oge_rg_table_check and the layout of the group keys, before anything is allocated or
+// launched), the per-record ReadEnds summaries allocated (`name` selects the buffer) and the RG table uploaded.
+int oge_markdup_prepare(oge_ctx *ctx, const oge_markdup_opts *opts, uint64_t n, const char *name, RecMeta **meta,
+                        OgeRgTable *rg);
+// The in-place dedup of n records: prepare, the input pass, then everything after it.
+int oge_markdup_run(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_markdup_opts *opts,
+                    uint8_t *d_dup, int apply, uint64_t *n_dup_out);
+// Everything after the per-record ReadEnds pass (oge_markdup_finish_pre without the fused gather's products).
+int oge_markdup_finish(oge_ctx *ctx, uint8_t *d_recs, const uint64_t *d_off, uint64_t n, const oge_markdup_opts *opts,
+                       const RecMeta *meta, uint8_t *d_dup, int apply, uint64_t *n_dup_out, uint64_t *d_desc, bool *desc_ok,
+                       const uint64_t *skeys);
+
 // skeys (optional): the records' coordinate sort keys when meta is in that sorted order; enables the
 // windowed group stages (oge_md_*_groups_win)
 int oge_md_cand_frag(oge_ctx *ctx, const oge_markdup_opts *opts, const RecMeta *meta, uint64_t n, bool want_desc,

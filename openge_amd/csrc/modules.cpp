@@ -9,7 +9,6 @@
 #include <cstdlib>
 #include <cerrno>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <functional>
 #include <atomic>
@@ -19,6 +18,7 @@
 #include <fcntl.h>
 
 #include "bam_layout.h"
+#include "lib_table.h"
 
 // realign.hip (C++): the realignment result's records and offsets moved out without a copy
 void oge_realign_result_take(oge_realign_result *r, oge::bytevec &recs, std::vector<uint64_t> &offs);
@@ -1002,74 +1002,42 @@ int FileReader::merge_inputs(ReadBatch &b, const std::vector<uint64_t> &file_end
 }
 
 // ----------------------------------------------------------------------------------- dedup opts
-// RG -> library table as MarkDuplicates::getLibraryName resolves it (mark_duplicates.cpp:301-318).
-struct MdOpts {
-    oge_markdup_opts o;
-    std::string ids;
-    std::vector<int16_t> libs;
-    std::vector<std::string> lib_names;  // by library id: "" where no @RG names the id (0, and an unknown_lib of its own)
-};
-static void markdup_opts(const BamHeaderModel &header, int32_t n_ref, bool compat, int split, MdOpts &m);
-static void markdup_opts(const ReadBatch &b, bool compat, int split, MdOpts &m) {
-    markdup_opts(b.header, (int32_t)b.ref_names.size(), compat, split, m);
-}
-static void markdup_opts(const BamHeaderModel &header, int32_t n_ref, bool compat, int split, MdOpts &m) {
-    std::map<std::string, int16_t> lib_ids;
-    int16_t next = 1;
-    for (auto &rg : header.rg) {
-        std::string lib = rg.lb.empty() ? std::string("Unknown Library") : rg.lb;
-        auto it = lib_ids.find(lib);
-        if (it == lib_ids.end()) it = lib_ids.emplace(lib, next++).first;
-        m.libs.push_back(it->second);
-        m.ids += rg.id;
-        m.ids.push_back('\0');
-    }
-    auto unk = lib_ids.find("Unknown Library");
-    m.libs.push_back(0);
-    memset(&m.o, 0, sizeof m.o);
-    m.o.n_ref = n_ref;
-    m.o.rg_ids = m.ids.c_str();
-    m.o.rg_ids_bytes = m.ids.size();
-    m.o.rg_lib = m.libs.data();
-    m.o.n_rg = (int32_t)header.rg.size();
-    m.o.unknown_lib = unk != lib_ids.end() ? unk->second : next;
-    m.o.compat_nonverbose_index = compat ? 1 : 0;
-    m.o.split_chains = split;
-    m.lib_names.assign((size_t)std::max<int16_t>(m.o.unknown_lib, (int16_t)(next - 1)) + 1, std::string());
-    for (auto &kv : lib_ids) m.lib_names[kv.second] = kv.first;
+// The dedup options of a batch: its header's RG -> library table (lib_table.h), which they point into
+static oge_markdup_opts markdup_opts(const LibTable &lt, const ReadBatch &b, bool compat, int split) {
+    return lt.opts((int32_t)b.ref_names.size(), compat ? 1 : 0, split);
 }
 
 // MarkDuplicates::metricsFilename: the module's counters sized and named for this header's libraries (once per
 // chain), and the counts of one more part of the marked output added to them
-static void metrics_begin(MarkDuplicates *md, const MdOpts &m) {
-    md->metricsLibraries = m.lib_names;
-    md->metricsUnknown = m.o.unknown_lib;
-    md->metrics.assign(m.lib_names.size(), OgeDupMetrics{});
+static void metrics_begin(MarkDuplicates *md, const LibTable &lt) {
+    md->metricsLibraries = lt.names;
+    md->metricsUnknown = lt.unknown_lib;
+    md->metrics.assign((size_t)lt.n_lib, OgeDupMetrics{});
     md->metricsMs = 0;
     if (md->opticalDistance >= 0) {
-        md->sets.assign(m.lib_names.size(), OgeDupSetsLib{});
+        md->sets.assign((size_t)lt.n_lib, OgeDupSetsLib{});
         md->setsHist.assign(3 * OGE_DUP_SETS_BINS, 0);
         md->setsMs = 0;
         md->setsTiers[0] = md->setsTiers[1] = md->setsTiers[2] = 0;
     }
 }
-static int metrics_count(MarkDuplicates *md, oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_offs, uint64_t n, const MdOpts &m) {
+static int metrics_count(MarkDuplicates *md, oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_offs, uint64_t n, const oge_markdup_opts &o) {
     std::vector<OgeDupMetrics> part(md->metrics.size());
-    if (oge_dup_metrics_dev(ctx, d_recs, d_offs, n, &m.o, (int32_t)part.size(), part.data())) return -1;
+    if (oge_dup_metrics_dev(ctx, d_recs, d_offs, n, &o, (int32_t)part.size(), part.data())) return -1;
     for (size_t k = 0; k < part.size(); ++k) add_metrics(md->metrics[k], part[k]);
     double ms = 0;
     if (!oge_ctx_timing(ctx, "dup_metrics", &ms) && ms > 0) md->metricsMs += ms;
     if (md->opticalDistance < 0) return 0;
     // --optical-distance: the duplicate sets of the same records, which are all resident here
-    if (oge_dup_sets_dev(ctx, d_recs, d_offs, n, &m.o, md->opticalDistance, (int32_t)md->sets.size(), md->sets.data(), md->setsHist.data())) return -1;
+    if (oge_dup_sets_dev(ctx, d_recs, d_offs, n, &o, md->opticalDistance, (int32_t)md->sets.size(), md->sets.data(), md->setsHist.data())) return -1;
     if (!oge_ctx_timing(ctx, "dup_sets", &ms) && ms > 0) md->setsMs = ms;
     const char *tiers[3] = {"dupsets_wave_sets", "dupsets_block_sets", "dupsets_host_sets"};
     for (int k = 0; k < 3; ++k) oge_ctx_counter(ctx, tiers[k], &md->setsTiers[k]);
     return 0;
 }
 
-// One row for every library an @RG names, one more "Unknown Library" row when none does and a record resolved to it
-// (names by library id, "" = not named); oge_dup_metrics_text sorts them.
+// One row for every library an @RG names, one more row for the unknown library when none does and a record
+// resolved to it (names by library id, "" = not named); oge_dup_metrics_text sorts them.
 // sets / hist (--optical-distance; sets by library id as m): the text of oge_dup_sets_text
 static int metrics_text(const std::vector<std::string> &names, int unknown, const std::vector<OgeDupMetrics> &m, const std::string &command_line,
                         std::string &text, const std::vector<OgeDupSetsLib> *sets = nullptr, const uint64_t *hist = nullptr) {
@@ -1105,7 +1073,24 @@ static int metrics_text(const std::vector<std::string> &names, int unknown, cons
     return 0;
 }
 
-static int write_text_file(const std::string &out, const std::vector<uint8_t> &text);
+// data[0, bytes) as the whole of a new file; on an error its message, no file left behind and -1
+static int write_whole_file(const std::string &path, const void *data, size_t bytes) {
+    FILE *f = fopen(path.c_str(), "wb");
+    const bool ok = f && fwrite(data, 1, bytes, f) == bytes;
+    if ((f && fclose(f) != 0) || !ok) {
+        fprintf(stderr, "openge: error writing %s: %s\n", path.c_str(), strerror(errno));
+        remove(path.c_str());
+        return -1;
+    }
+    return 0;
+}
+// the same bytes to the standard output, flushed, when `out` is "stdout" or "-"; else to the file of that name
+static int write_stdout_or_file(const std::string &out, const void *data, size_t bytes) {
+    if (out != "stdout" && out != "-") return write_whole_file(out, data, bytes);
+    if (fwrite(data, 1, bytes, stdout) == bytes && fflush(stdout) == 0 && !ferror(stdout)) return 0;
+    fprintf(stderr, "openge: error writing to stdout\n");
+    return -1;
+}
 
 int MarkDuplicates::writeMetrics() const {
     std::string text;
@@ -1114,7 +1099,7 @@ int MarkDuplicates::writeMetrics() const {
         fprintf(stderr, "openge: MarkDuplicates: metrics: %s\n", oge_last_error(nullptr));
         return -1;
     }
-    if (write_text_file(metricsFilename, std::vector<uint8_t>(text.begin(), text.end()))) return -1;
+    if (write_whole_file(metricsFilename, text.data(), text.size())) return -1;
     if (verbose_) fprintf(stderr, "[openge] MarkDuplicates: metrics of %zu libraries to %s, stage dup_metrics %.3f ms\n",
                           (size_t)std::count_if(metricsLibraries.begin(), metricsLibraries.end(), [](const std::string &s) { return !s.empty(); }),
                           metricsFilename.c_str(), metricsMs);
@@ -1262,13 +1247,14 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
     }
     MarkDuplicates *md = order_ == BamHeaderModel::COORDINATE ? dynamic_cast<MarkDuplicates *>(sink_) : nullptr;
     if (cc.gpus > 1 && order_ == BamHeaderModel::COORDINATE) {  // --gpus G: range-split sort (+ dedup) over G ranks
-        MdOpts m;
-        if (md) markdup_opts(b, md->compatNonverbose, md->splitChains, m);
+        const LibTable lt(b.header);
+        oge_markdup_opts o = {};
+        if (md) o = markdup_opts(lt, b, md->compatNonverbose, md->splitChains);
         const bool count = md && !md->metricsFilename.empty();
-        if (count) metrics_begin(md, m);
+        if (count) metrics_begin(md, lt);
         uint64_t nd = 0;
         const auto t0 = clk();
-        if (run_ranks(cc, b, true, md ? &m.o : nullptr, &nd, count ? &md->metrics : nullptr, count ? &md->metricsMs : nullptr)) return -1;
+        if (run_ranks(cc, b, true, md ? &o : nullptr, &nd, count ? &md->metrics : nullptr, count ? &md->metricsMs : nullptr)) return -1;
         if (md) md->duplicates = nd;
         b.header.sort_order = order_;
         if (verbose_)
@@ -1290,17 +1276,18 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
         auto arena = std::make_shared<ReadBatch>();
         arena->recs = std::move(b.recs);
         arena->offs = std::move(b.offs);
-        auto mo = std::make_shared<MdOpts>();
-        if (md) markdup_opts(b, md->compatNonverbose, md->splitChains, *mo);
+        const auto lt = std::make_shared<LibTable>(b.header);  // lives as long as the closure whose options point into it
+        oge_markdup_opts mo = {};
+        if (md) mo = markdup_opts(*lt, b, md->compatNonverbose, md->splitChains);
         const char *ce = getenv("OGE_CHUNK_BYTES");
         const uint64_t chunk = ce ? strtoull(ce, nullptr, 10) : 0, n = b.n;
         const int32_t n_ref = (int32_t)b.ref_names.size();
-        b.produce = [arena, mo, md, chunk, n, n_ref](ChainContext &c, const ReadBatch::RangeSink &sink) -> int {
+        b.produce = [arena, lt, mo, md, chunk, n, n_ref](ChainContext &c, const ReadBatch::RangeSink &sink) -> int {
             // --metrics: every marked range is counted in front of the sink (which may drop its duplicates)
             const bool count = md && !md->metricsFilename.empty();
-            if (count) metrics_begin(md, *mo);
+            if (count) metrics_begin(md, *lt);
             const ReadBatch::RangeSink counted = [&](const uint8_t *r, const uint64_t *o, uint64_t m) -> int {
-                if (metrics_count(md, c.ctx, r, o, m, *mo)) return c.fail("MarkDuplicates: metrics");
+                if (metrics_count(md, c.ctx, r, o, m, mo)) return c.fail("MarkDuplicates: metrics");
                 return sink(r, o, m);
             };
             struct Tramp {
@@ -1308,7 +1295,7 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
                 static int call(void *u, const uint8_t *r, const uint64_t *o, uint64_t m) { return (*((Tramp *)u)->s)(r, o, m); }
             } tr{count ? &counted : &sink};
             uint64_t nd = 0, runs = 0, ranges = 0;
-            const int rc = oge_sort_markdup_chunked(c.ctx, arena->recs.data(), arena->offs.data(), n, n_ref, md ? &mo->o : nullptr,
+            const int rc = oge_sort_markdup_chunked(c.ctx, arena->recs.data(), arena->offs.data(), n, n_ref, md ? &mo : nullptr,
                                                     chunk, &Tramp::call, &tr, &nd, &runs, &ranges);
             if (rc) return c.fail("ReadSorter (chunked)");
             if (md) md->duplicates = nd;
@@ -1332,14 +1319,15 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
     if (verbose_) oge_ctx_sync(cc.ctx);
     const auto t1a = clk();
     int rc;
-    MdOpts m;
+    const LibTable lt(b.header);
+    oge_markdup_opts m = {};
     if (order_ == BamHeaderModel::QUERYNAME) {  // -b; a MarkDuplicates sink then runs on its own
         rc = oge_sort_name_dev(cc.ctx, b.d_recs, b.d_offs, b.n, perm);
         if (!rc) rc = oge_gather_records_dev(cc.ctx, b.d_recs, b.d_offs, perm, b.n, out, out_off);
     } else if (md) {  // mergesort -M: one fused device pipeline (sort, dedup, gather with 0x400 applied)
-        markdup_opts(b, md->compatNonverbose, md->splitChains, m);
+        m = markdup_opts(lt, b, md->compatNonverbose, md->splitChains);
         uint64_t nd = 0;
-        rc = oge_sort_markdup_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &m.o, perm, out, out_off, &nd);
+        rc = oge_sort_markdup_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &m, perm, out, out_off, &nd);
         md->duplicates = nd;
     } else {
         rc = oge_sort_coord_dev(cc.ctx, b.d_recs, b.d_offs, b.n, (int32_t)b.ref_names.size(), perm);
@@ -1359,7 +1347,7 @@ int ReadSorter::runInternal(ChainContext &cc, ReadBatch &b) {
     }
     if (rc) return cc.fail("ReadSorter");
     if (md && order_ == BamHeaderModel::COORDINATE && !md->metricsFilename.empty()) {  // --metrics: the marked output, before any removal
-        metrics_begin(md, m);
+        metrics_begin(md, lt);
         if (metrics_count(md, cc.ctx, out, out_off, b.n, m)) return cc.fail("MarkDuplicates: metrics");
     }
     cc.free_device(b);
@@ -1378,12 +1366,12 @@ int MarkDuplicates::runInternal(ChainContext &cc, ReadBatch &b) {
             fprintf(stderr, "openge: --compat-nonverbose-dedup is one-GPU only\n");
             return -1;
         }
-        MdOpts m;
-        markdup_opts(b, false, splitChains, m);
+        const LibTable lt(b.header);
+        const oge_markdup_opts m = markdup_opts(lt, b, false, splitChains);
         const bool count = !metricsFilename.empty();
-        if (count) metrics_begin(this, m);
+        if (count) metrics_begin(this, lt);
         uint64_t nd = 0;
-        if (run_ranks(cc, b, false, &m.o, &nd, count ? &metrics : nullptr, count ? &metricsMs : nullptr)) return -1;
+        if (run_ranks(cc, b, false, &m, &nd, count ? &metrics : nullptr, count ? &metricsMs : nullptr)) return -1;
         duplicates = nd;
         b.drop_duplicates = removeDuplicates;
         return 0;
@@ -1391,13 +1379,13 @@ int MarkDuplicates::runInternal(ChainContext &cc, ReadBatch &b) {
     if (cc.to_device(b)) return -1;
     DevBuf dup(cc.ctx);
     if (dup.alloc(b.n + 1)) return cc.fail("device allocation");
-    MdOpts m;
-    markdup_opts(b, compatNonverbose, splitChains, m);
+    const LibTable lt(b.header);
+    const oge_markdup_opts m = markdup_opts(lt, b, compatNonverbose, splitChains);
     uint64_t nd = 0;
-    if (oge_markdup_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &m.o, dup.as<uint8_t>(), 1, &nd) || oge_ctx_sync(cc.ctx)) return cc.fail("MarkDuplicates");
+    if (oge_markdup_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &m, dup.as<uint8_t>(), 1, &nd) || oge_ctx_sync(cc.ctx)) return cc.fail("MarkDuplicates");
     duplicates = nd;
     if (!metricsFilename.empty()) {  // the records carry their final FLAG now; -r drops them in the writer
-        metrics_begin(this, m);
+        metrics_begin(this, lt);
         if (metrics_count(this, cc.ctx, b.d_recs, b.d_offs, b.n, m)) return cc.fail("MarkDuplicates: metrics");
     }
     b.host_valid = false;
@@ -1434,7 +1422,6 @@ static int realign_ranks(ChainContext &cc, ReadBatch &b, const std::string &ht, 
 }
 
 static void report_targets(const oge_targets_result &r, int max_interval, int gap);
-static int write_text_file(const std::string &out, const std::vector<uint8_t> &text);
 
 // --auto-targets: the intervals of `openge targets` at its defaults, from the batch where it lies (the device
 // form when it is valid, else through the host form), written to <tmpdir>/oge_targets_<pid>.intervals.
@@ -1485,7 +1472,7 @@ int LocalRealignment::auto_targets(ChainContext &cc, ReadBatch &b, std::string &
     *n_targets = res.targets;
     if (!res.targets) return 0;
     path = tmpdir_ + (tmpdir_.empty() || tmpdir_.back() == '/' ? "" : "/") + "oge_targets_" + std::to_string((long long)getpid()) + ".intervals";
-    return write_text_file(path, text);
+    return write_whole_file(path, text.data(), text.size());
 }
 
 int LocalRealignment::runInternal(ChainContext &cc, ReadBatch &b) {
@@ -2059,16 +2046,8 @@ int FileWriter::runInternal(ChainContext &cc, ReadBatch &b) {
         fprintf(stderr, "openge: error writing %s: %s\n", filename_.c_str(), strerror(errno));
         return -1;
     }
-    if (index_) {  // only beside a BAM that was written whole
-        const std::string ip = filename_ + ".bai";
-        FILE *fi = fopen(ip.c_str(), "wb");
-        const bool ok = fi && fwrite(bai_.data(), 1, bai_.size(), fi) == bai_.size();
-        if ((fi && fclose(fi) != 0) || !ok) {
-            fprintf(stderr, "openge: error writing %s: %s\n", ip.c_str(), strerror(errno));
-            remove(ip.c_str());
-            return -1;
-        }
-    }
+    // only beside a BAM that was written whole
+    if (index_ && write_whole_file(filename_ + ".bai", bai_.data(), bai_.size())) return -1;
     if (verbose_ && on_device)
         fprintf(stderr, "[openge] FileWriter: device bins + BGZF %.3f s (gpu, segmented), device->host %.3f s, waiting on the disk %.3f s, "
                 "total %.3f s\n", t_dev, t_d2h, t_wait, sec(t2, clk()));
@@ -2106,14 +2085,7 @@ int index_bam_file(ChainContext &cc, const std::string &path, const std::string 
     }
     z.buf.reset();
     if (rc) return cc.fail("index");
-    FILE *f = fopen(out.c_str(), "wb");
-    const bool ok = f && fwrite(img.data(), 1, img.size(), f) == img.size();
-    if ((f && fclose(f) != 0) || !ok) {
-        fprintf(stderr, "openge: error writing %s: %s\n", out.c_str(), strerror(errno));
-        remove(out.c_str());
-        return -1;
-    }
-    return 0;
+    return write_whole_file(out, img.data(), img.size());
 }
 
 // ---- stats / count / coverage ------------------------------------------------------------------------
@@ -2162,15 +2134,15 @@ struct QcInput {
         return oge_targets_dev(cc.ctx, b.d_recs, b.d_offs, b.n, (int32_t)sam_lens.size(), sam_lens.data(), sam_names.data(), sam_names.size(), o,
                                res, d_targets, d_text);
     }
-    // the counters by library id, the ids' names ("" = no @RG names it) and the id of "Unknown Library"
+    // the counters by library id, the ids' names ("" = no @RG names it) and unknown_lib, as LibTable gives them
     int dup_metrics(std::vector<OgeDupMetrics> &m, std::vector<std::string> &names, int *unknown) {
         if (sam) {
-            MdOpts mo;
-            markdup_opts(b, false, 0, mo);
-            names = mo.lib_names;
-            *unknown = mo.o.unknown_lib;
-            m.assign(names.size(), OgeDupMetrics{});
-            return oge_dup_metrics_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &mo.o, (int32_t)m.size(), m.data());
+            const LibTable lt(b.header);
+            const oge_markdup_opts mo = markdup_opts(lt, b, false, 0);
+            names = lt.names;
+            *unknown = lt.unknown_lib;
+            m.assign((size_t)lt.n_lib, OgeDupMetrics{});
+            return oge_dup_metrics_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &mo, lt.n_lib, m.data());
         }
         const OgeDupMetrics *out = nullptr;
         const char *nm = nullptr;
@@ -2187,21 +2159,20 @@ struct QcInput {
         *unknown = unk;
         return 0;
     }
-    // --optical-distance: the duplicate sets, n_lib entries as dup_metrics numbered them (the same header)
-    int dup_sets(int64_t distance, int32_t n_lib, std::vector<OgeDupSetsLib> &s, std::vector<uint64_t> &hist) {
+    // --optical-distance: the duplicate sets by library id, the ids of dup_metrics (one header, one LibTable)
+    int dup_sets(int64_t distance, std::vector<OgeDupSetsLib> &s, std::vector<uint64_t> &hist) {
         if (sam) {
-            MdOpts mo;
-            markdup_opts(b, false, 0, mo);
-            s.assign((size_t)n_lib, OgeDupSetsLib{});
+            const LibTable lt(b.header);
+            const oge_markdup_opts mo = markdup_opts(lt, b, false, 0);
+            s.assign((size_t)lt.n_lib, OgeDupSetsLib{});
             hist.assign(3 * OGE_DUP_SETS_BINS, 0);
-            return oge_dup_sets_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &mo.o, distance, n_lib, s.data(), hist.data());
+            return oge_dup_sets_dev(cc.ctx, b.d_recs, b.d_offs, b.n, &mo, distance, lt.n_lib, s.data(), hist.data());
         }
         const OgeDupSetsLib *out = nullptr;
         const uint64_t *h = nullptr;
         int32_t got = 0;
         const int rc = oge_bam_dup_sets_dev(cc.ctx, z.buf.as<uint8_t>(), z.zbytes, distance, &out, &h, &got);
         if (rc) return rc;
-        if (got != n_lib) return -1;
         s.assign(out, out + got);
         hist.assign(h, h + 3 * OGE_DUP_SETS_BINS);
         return 0;
@@ -2347,17 +2318,6 @@ static void report_targets(const oge_targets_result &r, int max_interval, int ga
             max_interval, (unsigned long long)r.targets, gap, (unsigned long long)r.text_bytes);
 }
 
-static int write_text_file(const std::string &out, const std::vector<uint8_t> &text) {
-    FILE *f = fopen(out.c_str(), "wb");
-    const bool ok = f && fwrite(text.data(), 1, text.size(), f) == text.size();
-    if ((f && fclose(f) != 0) || !ok) {
-        fprintf(stderr, "openge: error writing %s: %s\n", out.c_str(), strerror(errno));
-        remove(out.c_str());
-        return -1;
-    }
-    return 0;
-}
-
 int targets_bam_file(ChainContext &cc, const std::string &path, const std::string &out, int max_interval, int gap) {
     QcInput in(cc);
     if (in.load(path)) return -1;
@@ -2377,15 +2337,7 @@ int targets_bam_file(ChainContext &cc, const std::string &path, const std::strin
     in.z.buf.reset();
     if (rc) return cc.fail("targets");
     const auto t0 = clk();
-    if (out == "stdout" || out == "-") {
-        const bool ok = fwrite(text.data(), 1, text.size(), stdout) == text.size() && fflush(stdout) == 0 && !ferror(stdout);
-        if (!ok) {
-            fprintf(stderr, "openge: error writing to stdout\n");
-            return -1;
-        }
-    } else if (write_text_file(out, text)) {
-        return -1;
-    }
+    if (write_stdout_or_file(out, text.data(), text.size())) return -1;
     if (cc.verbose) report_targets(res, max_interval, gap);
     report_stages(cc, "targets", sec(t0, clk()));
     return 0;
@@ -2405,7 +2357,7 @@ int dupmetrics_bam_file(ChainContext &cc, const std::string &path, const std::st
     double metrics_ms = 0;
     if (!rc && optical) {  // the same file once more: the duplicate sets of its records
         oge_ctx_timing(cc.ctx, "dup_metrics", &metrics_ms);
-        rc = in.dup_sets(optical_distance, (int32_t)m.size(), sets, hist);
+        rc = in.dup_sets(optical_distance, sets, hist);
     }
     in.z.buf.reset();
     if (rc) return cc.fail("dupmetrics");
@@ -2415,15 +2367,7 @@ int dupmetrics_bam_file(ChainContext &cc, const std::string &path, const std::st
         fprintf(stderr, "openge: dupmetrics: %s\n", oge_last_error(nullptr));
         return -1;
     }
-    if (out == "stdout" || out == "-") {
-        const bool ok = fwrite(text.data(), 1, text.size(), stdout) == text.size() && fflush(stdout) == 0 && !ferror(stdout);
-        if (!ok) {
-            fprintf(stderr, "openge: error writing to stdout\n");
-            return -1;
-        }
-    } else if (write_text_file(out, std::vector<uint8_t>(text.begin(), text.end()))) {
-        return -1;
-    }
+    if (write_stdout_or_file(out, text.data(), text.size())) return -1;
     report_stages(cc, optical ? "dup_sets" : "dup_metrics", sec(t0, clk()));
     if (cc.verbose && optical) {
         uint64_t tiers[3] = {0, 0, 0};

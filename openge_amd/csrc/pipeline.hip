@@ -25,50 +25,15 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "bamio.h"
 #include "bgzf_dev.h"
+#include "lib_table.h"
 #include "oge_ctx.h"
 
 using namespace oge;
-
-namespace {
-
-// MarkDuplicates::getLibraryName (algorithms/mark_duplicates.cpp:301-318): the LB of the record's
-// @RG, "Unknown Library" when absent or empty; distinct names get distinct ids.
-struct LibTable {
-    std::string ids;
-    std::vector<int16_t> libs;
-    oge_markdup_opts o;
-    LibTable(const BamHeaderModel &h, int32_t n_ref, const oge_mergesort_opts *mo) {
-        std::map<std::string, int16_t> lib_ids;
-        int16_t next = 1;
-        for (auto &rg : h.rg) {
-            const std::string lib = rg.lb.empty() ? std::string("Unknown Library") : rg.lb;
-            auto it = lib_ids.find(lib);
-            if (it == lib_ids.end()) it = lib_ids.emplace(lib, next++).first;
-            libs.push_back(it->second);
-            ids += rg.id;
-            ids.push_back('\0');
-        }
-        auto unk = lib_ids.find("Unknown Library");
-        libs.push_back(0);
-        memset(&o, 0, sizeof o);
-        o.n_ref = n_ref;
-        o.rg_ids = ids.c_str();
-        o.rg_ids_bytes = ids.size();
-        o.rg_lib = libs.data();
-        o.n_rg = (int32_t)h.rg.size();
-        o.unknown_lib = unk != lib_ids.end() ? unk->second : next;
-        o.compat_nonverbose_index = mo->compat_nonverbose_index;
-        o.split_chains = mo->split_chains;
-    }
-};
-
-}  // namespace
 
 extern "C" void oge_mergesort_opts_init(oge_mergesort_opts *o) {
     if (!o) return;
@@ -206,10 +171,11 @@ static int sort_stage(oge_ctx *ctx, uint8_t *X, uint64_t *xoff, uint64_t n, uint
     uint32_t *perm = (uint32_t *)ctx->ws("pipe_perm", (n + 1) * 4);
     if (!Y || !yoff || !perm) return OGE_ERR_HIP;
     *nd = 0;
-    LibTable lt(f.header, n_ref, mo);
     int rc;
     if (mo->mark_duplicates) {
-        rc = oge_sort_markdup_dev(ctx, X, xoff, n, &lt.o, perm, Y, yoff, nd);
+        const LibTable lt(f.header);
+        const oge_markdup_opts o = lt.opts(n_ref, mo->compat_nonverbose_index, mo->split_chains);
+        rc = oge_sort_markdup_dev(ctx, X, xoff, n, &o, perm, Y, yoff, nd);
     } else {
         rc = oge_sort_coord_dev(ctx, X, xoff, n, n_ref, perm);
         if (!rc) rc = oge_gather_records_dev(ctx, X, xoff, perm, n, Y, yoff);
@@ -390,23 +356,18 @@ extern "C" int oge_bam_dup_metrics_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_
     BamFile f;
     int rc = decode_for_qc(ctx, d_z, zbytes, &X, &xoff, &n, &f);
     if (rc) return rc;
-    oge_mergesort_opts mo;
-    oge_mergesort_opts_init(&mo);
-    const LibTable lt(f.header, (int32_t)f.ref_names.size(), &mo);
-    int16_t top = lt.o.unknown_lib;
-    for (size_t g = 0; g < f.header.rg.size(); ++g) top = std::max(top, lt.libs[g]);
-    std::vector<std::string> names((size_t)top + 1);
-    for (size_t g = 0; g < f.header.rg.size(); ++g) names[lt.libs[g]] = f.header.rg[g].lb.empty() ? std::string("Unknown Library") : f.header.rg[g].lb;
-    ctx->dm_out.assign((size_t)top + 1, OgeDupMetrics{});
+    const LibTable lt(f.header);
+    const oge_markdup_opts o = lt.opts((int32_t)f.ref_names.size());
+    ctx->dm_out.assign((size_t)lt.n_lib, OgeDupMetrics{});
     ctx->dm_names.clear();
-    for (const std::string &s : names) ctx->dm_names.append(s.c_str(), s.size() + 1);
-    rc = oge_dup_metrics_impl(ctx, X, xoff, n, &lt.o, (int32_t)top + 1, ctx->dm_out.data());
+    for (const std::string &s : lt.names) ctx->dm_names.append(s.c_str(), s.size() + 1);
+    rc = oge_dup_metrics_impl(ctx, X, xoff, n, &o, lt.n_lib, ctx->dm_out.data());
     if (rc) return rc;
     *out = ctx->dm_out.data();
-    *n_lib = (int32_t)top + 1;
+    *n_lib = lt.n_lib;
     *lib_names = ctx->dm_names.data();
     *names_bytes = ctx->dm_names.size();
-    *unknown_lib = lt.o.unknown_lib;
+    *unknown_lib = lt.unknown_lib;
     return OGE_OK;
 }
 
@@ -423,18 +384,15 @@ extern "C" int oge_bam_dup_sets_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t z
     BamFile f;
     int rc = decode_for_qc(ctx, d_z, zbytes, &X, &xoff, &n, &f);
     if (rc) return rc;
-    oge_mergesort_opts mo;
-    oge_mergesort_opts_init(&mo);
-    const LibTable lt(f.header, (int32_t)f.ref_names.size(), &mo);
-    int16_t top = lt.o.unknown_lib;
-    for (size_t g = 0; g < f.header.rg.size(); ++g) top = std::max(top, lt.libs[g]);
-    ctx->ds_out.assign((size_t)top + 1, OgeDupSetsLib{});
+    const LibTable lt(f.header);
+    const oge_markdup_opts o = lt.opts((int32_t)f.ref_names.size());
+    ctx->ds_out.assign((size_t)lt.n_lib, OgeDupSetsLib{});
     ctx->ds_hist.assign(3 * OGE_DUP_SETS_BINS, 0);
-    rc = oge_dup_sets_impl(ctx, X, xoff, n, &lt.o, distance, (int32_t)top + 1, ctx->ds_out.data(), ctx->ds_hist.data());
+    rc = oge_dup_sets_impl(ctx, X, xoff, n, &o, distance, lt.n_lib, ctx->ds_out.data(), ctx->ds_hist.data());
     if (rc) return rc;
     *out_per_lib = ctx->ds_out.data();
     *hist = ctx->ds_hist.data();
-    *n_lib = (int32_t)top + 1;
+    *n_lib = lt.n_lib;
     return OGE_OK;
 }
 
@@ -649,11 +607,12 @@ static int dist_sort_write(oge_comm *comm, int rc, const std::string &why, uint8
     oge_ctx *ctx = oge_comm_ctx(comm);
     const int rank = oge_comm_rank(comm), G = oge_comm_size(comm);
     const int32_t n_ref = (int32_t)f.ref_names.size();
-    LibTable lt(f.header, n_ref, mo);
+    const LibTable lt(f.header);
+    const oge_markdup_opts o = lt.opts(n_ref, mo->compat_nonverbose_index, mo->split_chains);
     uint8_t *dout = nullptr;
     uint64_t *doff = nullptr, no = 0, nd = 0;
     const int rd = oge_sort_markdup_dist(comm, rc ? nullptr : X, rc ? nullptr : xoff, rc ? 0 : n, n_ref, 1,
-                                         mo->mark_duplicates ? &lt.o : nullptr, &dout, &doff, &no, &nd);
+                                         mo->mark_duplicates ? &o : nullptr, &dout, &doff, &no, &nd);
     if (rc) return oge_fail(ctx, rc, why.c_str());
     if (rd) return rd;
     const uint8_t *src = dout;

@@ -2,6 +2,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/openge_hip.h"
+
 // RecMeta.m (u64):
 //   [0,16)  score (int16, getScore)        [16,32) library id
 //   bit 32 fragment ReadEnds exists (mapped, refID != -1, primary)   bit 33 reverse strand
@@ -42,6 +44,15 @@ struct OgeRgTable {
     int16_t unknown_lib;
     int32_t split_k;  // > 1: split-by-chromosome emulation, the pair key carries the chain refID % K
 };
+struct oge_ctx;
+// The read-group fields of a caller's options (markdup.hip), checked before anything is allocated or launched:
+// the pointers, at most OGE_MAX_RG groups, every library id (unknown_lib, then rg_lib[g]) inside [0, n_lib) --
+// with n_lib = 0 only non-negative -- and the ids n_rg NUL-terminated strings within rg_ids_bytes.  `who`
+// prefixes the message.
+int oge_rg_table_check(oge_ctx *ctx, const oge_markdup_opts *opts, const char *who, int32_t n_lib);
+// The checked table laid out and copied up, complete on return, into the workspaces "<ws>_rgids", "<ws>_rgidw",
+// "<ws>_rgoff" and "<ws>_rglib": "md" for the dedup, "dm" for the metrics (a dedup in flight keeps its table).
+int oge_rg_table_upload(oge_ctx *ctx, const oge_markdup_opts *opts, const char *ws, OgeRgTable *rg);
 
 // Sort-key packing of the KEYS output (see sort.hip for the layout).
 constexpr uint64_t OGE_SORT_KEY_MASK = (1ull << 50) - 1;
@@ -82,7 +93,6 @@ struct OgePassArgs {
     int32_t cf_split;
 };
 
-struct oge_ctx;
 // oge_sort_keys_dev_hook: called after the tie sort with the final permutation (perm[k] = input index of
 // output record k) and the sorted keys; it gathers the summaries itself (and whatever it derives from them)
 struct OgeSortGatherHook {
@@ -90,6 +100,25 @@ struct OgeSortGatherHook {
     void *user;
 };
 int oge_input_pass(oge_ctx *ctx, const OgePassArgs &a);
+// The coordinate sort (sort.hip).  oge_sort_buffers: the (key, value) buffers it reads its input from;
+// oge_sort_counts: its status words (the `bad` word of the KEYS pass first).
+int oge_sort_buffers(oge_ctx *ctx, uint64_t n, uint64_t **keys, uint32_t **vals);
+unsigned int *oge_sort_counts(oge_ctx *ctx);
+// Sort keys/vals for records; on return *kout/*vout hold the sorted (key, input index) pairs.
+// keys_ready: the KEYS pass (records.hip) already filled oge_sort_buffers and the `bad` word.
+// With meta_in/meta_out, meta_out receives the summaries in output order, and the small tie runs
+// are ordered on them (k_ties_meta) instead of on the record bytes.
+int oge_sort_keys_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref,
+                      bool keys_ready, uint64_t **kout, uint32_t **vout, const RecMeta *meta_in = nullptr,
+                      RecMeta *meta_out = nullptr);
+// With a gather hook (the fused sort + dedup pipeline): the summaries are gathered by hook->fn AFTER the
+// tie sort, in final order, instead of by oge_meta_gather before it (see k_ties_meta<false>); meta_out is
+// then not written here.
+int oge_sort_keys_dev_hook(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref,
+                           bool keys_ready, uint64_t **kout, uint32_t **vout, const RecMeta *meta_in, RecMeta *meta_out,
+                           const OgeSortGatherHook *hook);
+// out[k] = in[perm[k]] (markdup.hip)
+int oge_meta_gather(oge_ctx *ctx, const RecMeta *in, const uint32_t *perm, uint64_t n, RecMeta *out);
 int oge_gather_pass(oge_ctx *ctx, const OgePassArgs &a);
 // Output offsets (from the sorted keys' size payload, or from the records) + the record gather.
 int oge_gather_with_sizes(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, const uint32_t *d_perm,

@@ -19,8 +19,6 @@
 #include <algorithm>
 #include <vector>
 
-unsigned int *oge_sort_counts(oge_ctx *ctx);
-
 namespace {
 
 constexpr uint64_t kSortKeyMask = OGE_SORT_KEY_MASK;
@@ -397,18 +395,7 @@ int oge_sort_buffers(oge_ctx *ctx, uint64_t n, uint64_t **keys, uint32_t **vals)
     return (*keys && *vals) ? OGE_OK : OGE_ERR_HIP;
 }
 
-// Sort keys/vals for records; on return *kout/*vout hold the sorted (key, input index) pairs.
-// keys_ready: the KEYS pass (records.hip) already filled oge_sort_buffers and the `bad` word.
-int oge_meta_gather(oge_ctx *ctx, const RecMeta *in, const uint32_t *perm, uint64_t n, RecMeta *out);
-
-// With meta_in/meta_out, meta_out receives the summaries in output order, and the small tie runs
-// are ordered on them (k_ties_meta) instead of on the record bytes.
-// With a gather hook (the fused sort + dedup pipeline): the summaries are gathered by hook->fn AFTER the
-// tie sort, in final order, instead of by oge_meta_gather before it (see k_ties_meta<false>); meta_out is
-// then not written here.
-int oge_sort_keys_dev_hook(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref,
-                           bool keys_ready, uint64_t **kout, uint32_t **vout, const RecMeta *meta_in, RecMeta *meta_out,
-                           const OgeSortGatherHook *hook);
+// The sort of the records' keys (records.h says what the arguments select).
 int oge_sort_keys_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref,
                       bool keys_ready, uint64_t **kout, uint32_t **vout, const RecMeta *meta_in, RecMeta *meta_out) {
     return oge_sort_keys_dev_hook(ctx, d_recs, d_off, n, n_ref, keys_ready, kout, vout, meta_in, meta_out, nullptr);

@@ -91,7 +91,7 @@ def record_counters(flag: int, refid: int) -> list[str]:
 
 # ------------------------------------------------------------------------------------------- the table
 def lib_table(header_text: str) -> tuple[dict[bytes, int], int, list[str]]:
-    """(read-group id -> library id, unknown_lib, names by id) as markdup_opts() of modules.cpp numbers them: ids
+    """(read-group id -> library id, unknown_lib, names by id) as LibTable (csrc/lib_table.h) numbers them: ids
     from 1 in the order the names first appear; an @RG without an LB, or with an empty one, is in "Unknown Library";
     unknown_lib is that name's id when an @RG has it, else the next free id, whose name here is ""."""
     ids: dict[str, int] = {}

@@ -106,6 +106,21 @@ def test_library_id_outside_the_table_is_an_argument_error(ctx):
     assert "error -1:" in str(e.value) and "read group 0" in str(e.value)
 
 
+def test_unterminated_read_group_ids_are_an_argument_error(ctx):
+    """two ids in six bytes of which rg_ids_bytes declares five: refused on the host, before anything is launched"""
+    header, records = CASES["n0"]
+    recs, offs = bamutil.pack_records(records)
+    ids = np.frombuffer(b"g1\0g2\0", np.uint8).copy()
+    libs = np.array([1, 1, 0], np.int16)
+    o = L.MarkdupOpts()
+    o.n_ref, o.rg_ids, o.rg_ids_bytes, o.rg_lib, o.n_rg, o.unknown_lib = len(K.REFS), ids.ctypes.data, 5, libs.ctypes.data, 2, 2
+    d = dev(recs, offs[:-1])
+    with pytest.raises(L.OgeError, match=r"error -1: .*not n_rg NUL-terminated"):
+        ctx.dup_metrics_dev(d[0].data_ptr(), d[1].data_ptr(), len(records), o, 3)
+    o.rg_ids_bytes = 6
+    assert as_lists(ctx.dup_metrics_dev(d[0].data_ptr(), d[1].data_ptr(), len(records), o, 3)) == [[0] * 6] * 3
+
+
 # ------------------------------------------------------------------------------------------------ the reference
 @functools.lru_cache(maxsize=None)
 def golden(name):

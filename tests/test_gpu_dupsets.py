@@ -130,6 +130,21 @@ def test_a_wider_table_and_the_refusals(ctx):
     assert got_lists(ctx.dup_sets(recs, offs, len(offs), opts, 100, 4)) == (per_lib, hist)
 
 
+def test_unterminated_read_group_ids_are_an_argument_error(ctx):
+    """two ids in six bytes of which rg_ids_bytes declares five: refused on the host, before anything is launched"""
+    header, recs, offs = packed("n0")
+    ids = np.frombuffer(b"g1\0g2\0", np.uint8).copy()
+    libs = np.array([1, 1, 0], np.int16)
+    o = L.MarkdupOpts()
+    o.n_ref, o.rg_ids, o.rg_ids_bytes, o.rg_lib, o.n_rg, o.unknown_lib = len(K.REFS), ids.ctypes.data, 5, libs.ctypes.data, 2, 2
+    d = dev(recs, offs)
+    with pytest.raises(L.OgeError, match=rf"error {ERR_ARG}: .*not n_rg NUL-terminated"):
+        ctx.dup_sets_dev(d[0].data_ptr(), d[1].data_ptr(), len(offs), o, 100, 3)
+    o.rg_ids_bytes = 6
+    per_lib, hist = got_lists(ctx.dup_sets_dev(d[0].data_ptr(), d[1].data_ptr(), len(offs), o, 100, 3))
+    assert per_lib == [[0] * 4] * 3 and not any(any(r) for r in hist)
+
+
 def test_text_equals_the_model(ctx):
     for name, D in (("chain", 100), ("libs_rgs_tiles", 100), ("n0", 100), ("block", 100)):
         header, recs, offs = packed(name)

@@ -230,6 +230,10 @@ def test_read_group_table_refusals(ctx):
     libs[1] = 1
     o.unknown_lib = -1
     _refused_everywhere(ctx, w.recs, w.offs, w.n, o, "negative library id", ERR_ARG)
+    # ids that end before the second one's NUL: the backing array keeps that byte, nothing outside it is read
+    ids2 = np.frombuffer(b"g1\0g2\0", np.uint8).copy()
+    o.unknown_lib, o.rg_ids, o.rg_ids_bytes = 2, ids2.ctypes.data, 5
+    _refused_everywhere(ctx, w.recs, w.offs, w.n, o, "not n_rg NUL-terminated", ERR_ARG)
     _w12_still_works(ctx)
 
 
