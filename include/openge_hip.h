@@ -717,6 +717,71 @@ int oge_targets(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const uin
 int oge_bam_targets_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const oge_targets_opts *opts,
                         oge_targets_result *result, const oge_target **d_targets, const uint8_t **d_text);
 
+/* ---- NM and MD tags of records in HBM (openge calmd, localrealign --calmd) -------------------------------------
+ * The edit distance (NM) and the mismatch string (MD) of every mapped record recomputed against the reference
+ * sequence, as `samtools calmd` does without its options (the reference has no such step: it removes MD from every
+ * read it moves, algorithms/local_realignment.cpp:881); DESIGN.md section 28, the model is tests/calmd_model.py.
+ * Reference: the FASTA at fasta_path through the realigner's loader (name up to the first blank, CR before LF
+ *   dropped, the last of a repeated name wins), a..z upper-cased; only the contigs the list names are kept.
+ * Passed through unchanged, byte for byte, and counted in `skipped`: FLAG 0x4 set; refID < 0 or pos < 0;
+ *   n_cigar_op == 0; l_seq == 0.  A record of a contig whose name the FASTA lacks is passed through too and counted
+ *   in `no_reference`.  Every other record is used.
+ * Walk of a used record: x = pos (reference), y = 0 (read), run u = 0, nm = 0, MD empty; the ops in order.
+ *   M, =, X  per base: x at or past the end of the loaded sequence ends the walk of this record there, for all later
+ *            ops too (MD closes with the current run).  Otherwise c1 = the read's 4-bit code, c2 = the code of the
+ *            reference byte in "=ACMGRSVTWYHKDBN" (any other byte: 15); c1 == 0, or c1 == c2 and c1 != 15, is a
+ *            match (u += 1); anything else appends decimal u and the reference byte, u = 0, nm += 1 (N against N is
+ *            a mismatch, as in samtools).
+ *   D of L   appends decimal u, '^' and the L reference bytes from x, cut at the end of the sequence; u = 0,
+ *            nm += L, x += L.       I: y += L, nm += L.     S: y += L.     N: x += L.     H, P: nothing.
+ *   At the end decimal u is appended (it may be "0").
+ * Tags: every tag is walked (A c C: 1 byte, s S: 2, i I f: 4, Z H: up to the NUL, B: subtype, count, elements) and
+ *   only the first tag named NM and the first named MD are looked at.  NM of an integer type (c C s S i I) whose
+ *   value equals nm stays where and as it is; otherwise an NM tag of whatever type is removed and a new one
+ *   appended at the record's end with the smallest unsigned type that holds nm (C, S, I).  MD of type Z whose bytes
+ *   equal the new string stays; otherwise it is removed and MD:Z appended, after the NM tag when one was appended.
+ *   Every other tag (UQ too) is copied unchanged, block_size is updated, no other core field changes (bin neither).
+ * Result: records (= n), skipped, no_reference, nm_changed and md_changed (a tag that was absent and is appended
+ *   counts), bytes_out.
+ * OGE_ERR_ARG (the message names the lowest such record): a used record with refID >= n_ref (checked before the
+ *   FASTA is asked for the contig), a block_size above OGE_MAX_BLOCK_SIZE (10000, what the readers admit), a CIGAR
+ *   that does not fit its block_size, a CIGAR op code above 8, bases,
+ *   qualities or tags that do not fit block_size (a tag cut by the record's end, an unknown type or B subtype, a
+ *   string without its NUL), or M I S = X op lengths that do not sum to l_seq; unknown option bits, no FASTA path,
+ *   names that are not n_ref NUL-terminated strings.  OGE_ERR_LIMIT, likewise named: a record whose block_size
+ *   would exceed OGE_MAX_BLOCK_SIZE (10000) after the update, or whose nm exceeds 2^32 - 1.  OGE_ERR_IO: the FASTA
+ *   cannot be read or holds no sequence.  Nothing is written for a call that fails.
+ * The FASTA is an argument of every call, not a call of its own: the context keeps the uploaded sequences and
+ *   uploads again only when the file's path, size or mtime or the contig list differ from the last call's, so a
+ *   caller has no load to order before its calls and none to repeat when the file changes.  Counter
+ *   (oge_ctx_counter) "calmd_ref_uploads" = the uploads of the context's lifetime up to and including this call.
+ * Stage name for oge_ctx_timing: "calmd"; nested in it "calmd_ref", "calmd_size" (with the scan), "calmd_emit". */
+typedef struct oge_calmd_opts {
+    int32_t threads; /* host threads that read and lay out the FASTA; 0: one per hardware thread */
+    uint32_t flags;  /* 0 */
+} oge_calmd_opts;
+void oge_calmd_opts_init(oge_calmd_opts *o);
+typedef struct oge_calmd_result {
+    uint64_t records, skipped, no_reference, nm_changed, md_changed, bytes_out;
+} oge_calmd_result;
+/* Records d_recs + d_off[i] (n offsets; the arena carries 16 bytes of slack behind the last record).  The contig
+ * list is the host's: the n_ref names one after the other, each NUL-terminated, names_bytes bytes in all (as
+ * oge_ctx_last_refs hands them out).  *d_out (device, result->bytes_out bytes and 16 of slack) and *d_out_off
+ * (device, n + 1 offsets from 0) belong to the context and are valid until the next call on it. */
+int oge_calmd_dev(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref, const char *ref_names,
+                  uint64_t names_bytes, const char *fasta_path, const oge_calmd_opts *opts, oge_calmd_result *result,
+                  const uint8_t **d_out, const uint64_t **d_out_off);
+/* Host-buffer form: uploads, computes, copies the records into recs_out (out_cap bytes) and their n + 1 offsets
+ * into off_out; OGE_ERR_LIMIT with *result filled when recs_out is too small, so a first call with out_cap 0 sizes
+ * the buffer. */
+int oge_calmd(oge_ctx *ctx, const uint8_t *recs, uint64_t rec_bytes, const uint64_t *rec_off, uint64_t n, int32_t n_ref,
+              const char *ref_names, uint64_t names_bytes, const char *fasta_path, const oge_calmd_opts *opts,
+              oge_calmd_result *result, uint8_t *recs_out, uint64_t out_cap, uint64_t *off_out);
+/* A whole BAM file resident in HBM (4-byte aligned): framing index, inflate, header, record walk, then the tags
+ * against the file's own reference list (which stays with the context for oge_ctx_last_refs). */
+int oge_bam_calmd_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const char *fasta_path, const oge_calmd_opts *opts,
+                      oge_calmd_result *result, const uint8_t **d_out, const uint64_t **d_out_off);
+
 /* ---- duplication metrics of marked records (dedup --metrics, mergesort -M --metrics, openge dupmetrics) ----
  * Picard MarkDuplicates' metrics file for records that already carry their final FLAG (the reference writes none,
  * algorithms/mark_duplicates.cpp); DESIGN.md section 26, the model is tests/dupmetrics_model.py.  The counts are

@@ -1554,6 +1554,69 @@ int LocalRealignment::runInternal(ChainContext &cc, ReadBatch &b) {
     return 0;
 }
 
+// ----------------------------------------------------------------------------------- CalMD
+static const char *kCalmdNoFit = "openge calmd: the input does not fit in HBM (the records, their rewritten copy and the reference "
+                                 "must be resident together); input larger than HBM is not provided\n";
+
+bool CalMD::fitsDevice(ChainContext &cc, const std::vector<std::string> &inputs, const std::string &reference) {
+    uint64_t need = 0, fr = 0, tot = 0;
+    struct stat st;
+    for (auto &in : inputs)
+        if (in != "stdin" && in != "-" && !stat(in.c_str(), &st) && S_ISREG(st.st_mode)) need += 2 * (uint64_t)st.st_size;
+    if (!stat(reference.c_str(), &st) && S_ISREG(st.st_mode)) need += (uint64_t)st.st_size;
+    if (oge_mem_info(cc.ctx, &fr, &tot) || need <= fr) return true;
+    fputs(kCalmdNoFit, stderr);
+    return false;
+}
+
+int CalMD::runInternal(ChainContext &cc, ReadBatch &b) {
+    if (cc.gpus > 1 || !b.slices.empty() || !b.shards.empty() || b.produce) {
+        fprintf(stderr, "openge calmd: one GPU with the records resident in HBM is required\n");
+        return -1;
+    }
+    const auto t0 = clk();
+    uint64_t fr = 0, tot = 0;
+    if (!b.dev_valid && !oge_mem_info(cc.ctx, &fr, &tot) && b.bytes() + b.n * 8 > fr) {
+        fputs(kCalmdNoFit, stderr);
+        return -1;
+    }
+    if (cc.to_device(b)) return -1;
+    std::string names;
+    for (auto &s : b.ref_names) names.append(s.c_str(), s.size() + 1);
+    oge_calmd_opts o;
+    oge_calmd_opts_init(&o);
+    o.threads = cc.threads;
+    const uint8_t *d_out = nullptr;
+    const uint64_t *d_off = nullptr;
+    if (oge_calmd_dev(cc.ctx, b.d_recs, b.d_offs, b.n, (int32_t)b.ref_names.size(), names.data(), names.size(), reference_.c_str(), &o, &result,
+                      &d_out, &d_off))
+        return cc.fail("CalMD");
+    double ms = 0;
+    oge_ctx_timing(cc.ctx, "calmd", &ms);
+    // the call's output belongs to the context: the batch takes a copy of its own in place of its records
+    cc.free_device(b);
+    DevBuf r(cc.ctx), of(cc.ctx);
+    if (r.alloc(result.bytes_out + 64) || of.alloc((b.n + 1) * 8)) {
+        fputs(kCalmdNoFit, stderr);
+        return -1;
+    }
+    if ((result.bytes_out && oge_memcpy(cc.ctx, r.as<void>(), d_out, result.bytes_out + 16, 3)) ||
+        oge_memcpy(cc.ctx, of.as<void>(), d_off, (b.n + 1) * 8, 3))
+        return cc.fail("CalMD");
+    b.d_recs = (uint8_t *)r.release();
+    b.d_offs = (uint64_t *)of.release();
+    b.d_bytes = result.bytes_out;
+    b.dev_valid = true;
+    b.host_valid = false;
+    if (verbose_)
+        fprintf(stderr, "[openge] CalMD: %llu records, %llu skipped, %llu without reference, NM changed in %llu, MD changed in %llu, %llu bytes "
+                        "out; device %.3f s, total %.3f s\n",
+                (unsigned long long)result.records, (unsigned long long)result.skipped, (unsigned long long)result.no_reference,
+                (unsigned long long)result.nm_changed, (unsigned long long)result.md_changed, (unsigned long long)result.bytes_out, ms / 1e3,
+                sec(t0, clk()));
+    return 0;
+}
+
 // ----------------------------------------------------------------------------------- FileWriter
 FileFormat detect_file_format(std::string name) {
     std::transform(name.begin(), name.end(), name.begin(), ::tolower);

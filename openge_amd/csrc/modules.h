@@ -264,6 +264,24 @@ protected:
     bool auto_targets_ = false;
 };
 
+// CalMD (`openge calmd`, `localrealign --calmd`; not in the reference, whose users follow it with `samtools calmd`):
+// the NM and MD tags of the batch recomputed against the reference FASTA on the GPU.  The batch goes to the device
+// if it is not there, one oge_calmd_dev call rewrites it, and the batch's device form is replaced by a copy of the
+// call's output (which belongs to the context).  One GPU; a batch that does not fit in HBM beside its output and
+// the reference is refused.
+class CalMD : public AlgorithmModule {
+public:
+    CalMD() : AlgorithmModule("CalMD") {}
+    void setReferenceFilename(const std::string &f) { reference_ = f; }
+    oge_calmd_result result{};
+    // before anything is read: false (with a message) when the inputs' files alone, twice over, and the FASTA
+    // exceed the free device memory -- the records and their rewritten copy are at least as large as the files
+    static bool fitsDevice(ChainContext &cc, const std::vector<std::string> &inputs, const std::string &reference);
+protected:
+    int runInternal(ChainContext &cc, ReadBatch &b) override;
+    std::string reference_;
+};
+
 // The multi-GPU form of ReadSorter (+ MarkDuplicates) and of a standalone MarkDuplicates: the batch
 // is cut into G contiguous input ranges, one per rank, and oge_sort_markdup_dist leaves b.slices.  With `metrics`
 // (n_lib entries, added to) every rank counts its own output slice and the host sums; *metrics_ms += the slowest

@@ -32,6 +32,19 @@ struct OgeContigTable {
     uint32_t n_slots = 0;
 };
 
+// The reference sequences the last oge_calmd call left on the device (calmd.hip): the FASTA they came from by path,
+// size and mtime, the contig list they were laid out for (the names NUL-terminated one after the other), the
+// sequences back to back in workspace "calmd_ref_bytes" with each contig's offset (-1: the FASTA lacks it) and
+// length.  `uploads` counts the uploads of the context's lifetime (counter "calmd_ref_uploads").
+struct OgeRefTable {
+    bool valid = false;
+    std::string path, names;
+    uint64_t size = 0, n_ref = 0, uploads = 0;
+    int64_t mtime = 0;
+    const uint8_t *d_bytes = nullptr;
+    const int64_t *d_off = nullptr, *d_len = nullptr;
+};
+
 struct oge_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -86,6 +99,7 @@ struct oge_ctx {
     OgeContigTable text_table{"text_names", "text_name_off", nullptr, "text_table_uploads"};
     OgeContigTable sam_table{"sam_names", "sam_name_off", "sam_slots", "sam_table_uploads"};
     OgeContigTable targets_table{"tg_names", "tg_name_off", nullptr, "targets_table_uploads"};  // oge_targets_dev's
+    OgeRefTable calmd_ref;              // oge_calmd_dev's reference
     std::vector<OgeDupMetrics> dm_out;  // what the last oge_bam_dup_metrics_dev call returned
     std::string dm_names;
     std::vector<OgeDupSetsLib> ds_out;  // what the last oge_bam_dup_sets_dev call returned
@@ -243,6 +257,12 @@ int oge_qc_coverage_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_
 int oge_targets_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref, const int32_t *ref_len,
                      const char *ref_names, uint64_t names_bytes, const oge_targets_opts *opts, oge_targets_result *result,
                      const oge_target **d_targets, const uint8_t **d_text);
+
+// ---- NM / MD tags (calmd.hip) ----
+// oge_calmd_dev without the context checks and the timing reset (oge_bam_calmd_dev calls it under its hold)
+int oge_calmd_impl(oge_ctx *ctx, const uint8_t *d_recs, const uint64_t *d_off, uint64_t n, int32_t n_ref, const char *ref_names,
+                   uint64_t names_bytes, const char *fasta_path, const oge_calmd_opts *opts, oge_calmd_result *result, const uint8_t **d_out,
+                   const uint64_t **d_out_off);
 
 // ---- duplication metrics (dupmetrics.hip) ----
 // oge_dup_metrics_dev without the context checks and the timing reset (oge_bam_dup_metrics_dev calls it under its hold)

@@ -21,6 +21,9 @@
 // reference never wrote (algorithms/mark_duplicates.cpp has no metrics code); `dupmetrics` writes it for a file that
 // is already marked (dupmetrics_bam_file, csrc/dupmetrics.hip).  --optical-distance N adds the
 // optical duplicates and the set-size histogram of the duplicate sets (csrc/dupsets.hip).
+// `calmd` (not in the reference, which removes MD from every read it moves and leaves the rest to `samtools calmd`) is
+// FileReader -> CalMD -> FileWriter: the NM and MD tags recomputed against -R on the GPU (csrc/calmd.hip; DESIGN.md
+// section 28); `localrealign --calmd` puts the same module between the realigner and the writer.
 //
 // Deliberate differences: view -B/-E cuts QUAL to the window of SEQ; the reference cuts the
 // qualities of the already shortened read a second time (algorithms/filter.cpp:188-189), which leaves fewer
@@ -89,7 +92,9 @@ const Opt kCoverage[] = {{"o", "out", true}, {"b", "binsize", true}, {"", "omitu
                          {"V", "verifymapping", false}, {"S", "strict", false}};
 const Opt kCompare[] = {{"r", "region", true}, {"p", "print", false}};
 const Opt kTargets[] = {{"o", "out", true}, {"", "maxinterval", true}, {"", "gap", true}};
-const Opt kRealign[] = {{"o", "out", true}, {"R", "reference", true}, {"L", "intervals", true}, {"", "auto-targets", false}};
+const Opt kRealign[] = {{"o", "out", true}, {"R", "reference", true}, {"L", "intervals", true}, {"", "auto-targets", false},
+                        {"", "calmd", false}};
+const Opt kCalmd[] = {{"o", "out", true}, {"R", "reference", true}, {"", "index", false}};
 
 struct Parsed {
     std::map<std::string, std::vector<std::string>> vm;  // long name -> values ("" for flags)
@@ -149,7 +154,7 @@ bool parse(int argc, const char **argv, const std::vector<Opt> &opts, Parsed &p)
 
 void usage_top() {
     fprintf(stderr, "Usage:\n    openge command [options]\n\nCommands: mergesort (alias: sort), dedup, localrealign, view, index, stats, count, coverage,\n"
-                    "          compare, targets, dupmetrics, version\n"
+                    "          compare, targets, dupmetrics, calmd, version\n"
                     "\n    Inputs are BAM files or SAM text (first byte '@'; also on stdin, and mixed with BAM files); SAM is parsed\n"
                     "    on the GPU.  index takes BAM only.\n"
                     "\n    openge view [-o out] [-n N] [-q MAPQ] [-l LEN] [-r REGION] [-L FILE] [-B N] [-E N] in.bam|in.sam\n"
@@ -183,6 +188,12 @@ void usage_top() {
                     "    openge localrealign -R ref.fa (-L targets.intervals | --auto-targets) [-T tmpdir] [-o out.bam] in.bam\n"
                     "                                        --auto-targets: the intervals of `openge targets` at its defaults,\n"
                     "                                        computed from the input's records (kept in a file in tmpdir meanwhile)\n"
+                    "    openge calmd -R ref.fa [-o out] [-F sam] [-c level] [--index] in.bam|in.sam\n"
+                    "                                        the NM and MD tags of every mapped read recomputed against ref.fa on\n"
+                    "                                        the GPU, as samtools calmd without options: a tag that is right\n"
+                    "                                        stays, any other is replaced at the record's end; BAM (default) or\n"
+                    "                                        SAM out; one GPU, the input resident in HBM\n"
+                    "    openge localrealign ... --calmd     the same step between the realigner and the writer, with its -R\n"
                     "    openge dedup --metrics FILE / mergesort|sort -M --metrics FILE\n"
                     "                                        also write Picard's duplication metrics of the marked records to\n"
                     "                                        FILE: per library the reads and pairs examined, the duplicates,\n"
@@ -235,6 +246,7 @@ int main(int argc, const char **argv) {
     else if (cmd == "compare") opts.insert(opts.end(), std::begin(kCompare), std::end(kCompare));
     else if (cmd == "targets") opts.insert(opts.end(), std::begin(kTargets), std::end(kTargets));
     else if (cmd == "dupmetrics") opts.insert(opts.end(), std::begin(kDupmetrics), std::end(kDupmetrics));
+    else if (cmd == "calmd") opts.insert(opts.end(), std::begin(kCalmd), std::end(kCalmd));
     else {
         fprintf(stderr, "Unknown command %s.\n", argv[1]);
         return -1;
@@ -277,7 +289,7 @@ int main(int argc, const char **argv) {
     const std::string out_name = p.get("out", "stdout");
     const bool out_stdout = out_name == "stdout" || out_name == "-";
     FileFormat fmt = FORMAT_BAM;
-    const bool chain_cmd = cmd == "view" || cmd == "mergesort" || cmd == "dedup" || cmd == "localrealign";
+    const bool chain_cmd = cmd == "view" || cmd == "mergesort" || cmd == "dedup" || cmd == "localrealign" || cmd == "calmd";
     if (chain_cmd) {
         if (p.count("format")) {
             FileWriter probe;
@@ -429,6 +441,17 @@ int main(int argc, const char **argv) {
         }
         optical_distance = d;
     }
+    const bool calmd = cmd == "calmd" || (cmd == "localrealign" && p.count("calmd"));
+    if (calmd) {  // refused before anything is read
+        if (cmd == "calmd" && (!p.count("reference") || p.vm["reference"].size() != 1)) {
+            fprintf(stderr, "openge calmd: one FASTA reference file is required (-R ref.fa)\n");
+            return -1;
+        }
+        if (cc.gpus > 1) {
+            fprintf(stderr, "openge %s: %s is not provided with --gpus\n", cmd.c_str(), cmd == "calmd" ? "calmd" : "--calmd");
+            return -1;
+        }
+    }
     if (cmd == "localrealign" && p.count("auto-targets") && p.count("intervals")) {
         fprintf(stderr, "openge localrealign: -L and --auto-targets exclude each other\n");
         return -1;
@@ -457,6 +480,10 @@ int main(int argc, const char **argv) {
     const char *pool = getenv("OGE_POOL");  // default on: the chain's modules share one memory pool
     if (!(pool && std::string(pool) == "0") && oge_ctx_set_pool(cc.ctx, 1)) {
         fprintf(stderr, "openge: %s\n", oge_last_error(cc.ctx));
+        return -1;
+    }
+    if (calmd && !CalMD::fitsDevice(cc, p.inputs, p.get("reference", ""))) {  // refused before anything is read
+        oge_ctx_destroy(cc.ctx);
         return -1;
     }
     if (cmd == "index") {
@@ -545,6 +572,12 @@ int main(int argc, const char **argv) {
         }
         ret = writer.runChain(cc);
         if (cc.verbose && dedup) fprintf(stderr, "Marked %llu records as duplicates.\n", (unsigned long long)md.duplicates);
+    } else if (cmd == "calmd") {
+        CalMD cm;
+        cm.setReferenceFilename(p.get("reference", ""));
+        reader.addSink(&cm);
+        cm.addSink(&writer);
+        ret = writer.runChain(cc);
     } else if (cmd == "dedup") {
         MarkDuplicates md;
         md.removeDuplicates = p.count("remove");
@@ -572,8 +605,15 @@ int main(int argc, const char **argv) {
         lr.setReferenceFilename(p.get("reference", ""));
         lr.setIntervalsFilename(p.get("intervals", ""));
         lr.setAutoTargets(auto_targets, p.get("tmpdir", "/tmp"));
+        CalMD cm;
+        cm.setReferenceFilename(p.get("reference", ""));
         reader.addSink(&lr);
-        lr.addSink(&writer);
+        if (calmd) {
+            lr.addSink(&cm);
+            cm.addSink(&writer);
+        } else {
+            lr.addSink(&writer);
+        }
         ret = writer.runChain(cc);
     }
     cc.close_ranks();

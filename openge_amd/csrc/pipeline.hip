@@ -344,6 +344,22 @@ extern "C" int oge_bam_targets_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zb
                             result, d_targets, d_text);
 }
 
+extern "C" int oge_bam_calmd_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const char *fasta_path, const oge_calmd_opts *opts,
+                                 oge_calmd_result *result, const uint8_t **d_out, const uint64_t **d_out_off) {
+    if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");
+    if (!opts || !result || !d_out || !d_out_off || (zbytes && !d_z)) return oge_fail(ctx, OGE_ERR_ARG, "null argument");
+    OgeCall call(ctx, /*hold=*/true);
+    *d_out = nullptr;
+    *d_out_off = nullptr;
+    uint8_t *X;
+    uint64_t *xoff, n;
+    BamFile f;
+    const int rc = decode_for_qc(ctx, d_z, zbytes, &X, &xoff, &n, &f);
+    if (rc) return rc;
+    return oge_calmd_impl(ctx, X, xoff, n, (int32_t)f.ref_names.size(), ctx->ref_names.data(), ctx->ref_names.size(), fasta_path, opts, result,
+                          d_out, d_out_off);
+}
+
 extern "C" int oge_bam_dup_metrics_dev(oge_ctx *ctx, const uint8_t *d_z, uint64_t zbytes, const OgeDupMetrics **out, int32_t *n_lib,
                                        const char **lib_names, uint64_t *names_bytes, int32_t *unknown_lib) {
     if (!ctx) return oge_fail(nullptr, OGE_ERR_ARG, "null ctx");

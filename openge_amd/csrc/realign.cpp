@@ -28,121 +28,10 @@
 #include <unordered_map>
 
 #include "bam_layout.h"
+#include "fasta.h"
+#include "host_pool.h"
 
 namespace oge {
-
-// The first call in a process touches every page of its per-read arrays for the first time (the scratch
-// keeps them for later calls): those are hvectors (uvector.h: 2 MiB pages, no serial zero fill on a
-// resize -- the workers that fill them touch their pages first).
-template <class T>
-using BigVec = hvector<T>;
-
-// =====================================================================================  threads
-// Persistent workers (kept across calls with the run's Scratch).  run_static maps index i to worker
-// i % size(); run hands indices out one at a time (prepare and decide: intervals differ in size; r03
-// mapped them statically so each interval's frees stayed in its allocating thread's arena -- the
-// interval objects are now reused instead of freed).
-static thread_local int tl_worker = 0;  // the Pool worker running the current job (0 = the caller)
-
-class Pool {
-public:
-    explicit Pool(int threads) {
-        if (threads <= 0) threads = (int)std::max(1u, std::thread::hardware_concurrency());
-        n_ = threads;
-        for (int t = 1; t < n_; ++t) ts_.emplace_back([this, t]() { loop(t); });
-    }
-    ~Pool() {
-        {
-            std::lock_guard<std::mutex> g(m_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto &t : ts_) t.join();
-    }
-    int size() const { return n_; }
-    template <class F>
-    void run_static(size_t n, F f) {
-        if (n_ == 1 || n <= 1) {
-            for (size_t i = 0; i < n; ++i) f(i);
-            return;
-        }
-        exec([&](int t) {
-            tl_worker = t;
-            for (size_t i = (size_t)t; i < n; i += (size_t)n_) f(i);
-        });
-    }
-    template <class F>
-    void run(size_t n, F f) {  // dynamic: indices handed out one at a time
-        if (n_ == 1 || n <= 1) {
-            for (size_t i = 0; i < n; ++i) f(i);
-            return;
-        }
-        std::atomic<size_t> next(0);
-        exec([&](int t) {
-            tl_worker = t;
-            for (size_t i; (i = next.fetch_add(1)) < n;) f(i);
-        });
-    }
-    template <class F>
-    void run_chunks(size_t n, size_t chunk, F f) {  // f(begin, end) over [0, n) in chunks
-        run((n + chunk - 1) / chunk, [&](size_t c) { f(c * chunk, std::min(n, (c + 1) * chunk)); });
-    }
-    // f(0..n) handed out in increasing order to the workers while the calling thread runs lead() beside them
-    // (and then helps with what is left); one thread: f over all, then lead
-    template <class F, class G>
-    void run_lead(size_t n, F f, G lead) {
-        if (n_ == 1) {
-            for (size_t i = 0; i < n; ++i) f(i);
-            lead();
-            return;
-        }
-        std::atomic<size_t> next(0);
-        exec([&](int t) {
-            tl_worker = t;
-            if (t == 0) lead();
-            for (size_t i; (i = next.fetch_add(1)) < n;) f(i);
-        });
-    }
-
-private:
-    void exec(const std::function<void(int)> &job) {
-        {
-            std::lock_guard<std::mutex> g(m_);
-            job_ = &job;
-            busy_ = n_ - 1;
-            gen_++;
-        }
-        cv_.notify_all();
-        job(0);
-        std::unique_lock<std::mutex> lk(m_);
-        done_.wait(lk, [&] { return busy_ == 0; });
-        job_ = nullptr;
-    }
-    void loop(int id) {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::function<void(int)> *job;
-            {
-                std::unique_lock<std::mutex> lk(m_);
-                cv_.wait(lk, [&] { return stop_ || gen_ != seen; });
-                if (stop_) return;
-                seen = gen_;
-                job = job_;
-            }
-            (*job)(id);
-            std::lock_guard<std::mutex> g(m_);
-            if (--busy_ == 0) done_.notify_one();
-        }
-    }
-    int n_ = 1;
-    std::vector<std::thread> ts_;
-    std::mutex m_;
-    std::condition_variable cv_, done_;
-    const std::function<void(int)> *job_ = nullptr;
-    int busy_ = 0;
-    uint64_t gen_ = 0;
-    bool stop_ = false;
-};
 
 // Hand the pages of a large block about to be freed back to the kernel from all workers: one
 // munmap of ~1 GB frees its pages serially.
@@ -385,107 +274,6 @@ static void tag_edit_i32(std::string &t, const char *tag, int32_t v) {
     tag_remove(t, tag);
     tag_add_int(t, tag, 'i', v, 4);
 }
-
-// =====================================================================================  FASTA
-// FastaReader (util/fasta_reader.cpp): sequences by name; readSequence(name, start, length) returns
-// the raw bytes (case preserved).
-struct Fasta {
-    std::unordered_map<std::string, std::string> seq;
-    BigVec<char> data;  // the file (kept, like the sequences' storage, for the next load: see Scratch; no zero
-                        // fill on a resize, the workers' preads touch its pages first)
-    size_t find_nl(size_t from) const {
-        if (from >= data.size()) return std::string::npos;
-        const void *q = memchr(data.data() + from, '\n', data.size() - from);
-        return q ? (size_t)((const char *)q - data.data()) : std::string::npos;
-    }
-    // Whole file in one read; contigs (">" lines) located serially, their bodies de-lined in
-    // parallel.  Line handling as FastaReader: name up to the first blank, CR before LF dropped.
-    bool load(const std::string &path, std::string &err, Pool &pool) {
-        FILE *f = fopen(path.c_str(), "rb");
-        if (!f) {
-            err = "cannot open reference FASTA " + path;
-            return false;
-        }
-        data.clear();
-        if (fseeko(f, 0, SEEK_END) == 0) {  // regular file: 8 MiB preads on the workers
-            const off_t sz = ftello(f);
-            if (sz > 0) {
-                data.resize((size_t)sz);
-                const int fd = fileno(f);
-                const size_t chunk = 8ull << 20;
-                std::atomic<bool> shortr(false);
-                pool.run_chunks((size_t)sz, chunk, [&](size_t o, size_t e) {
-                    while (o < e) {
-                        const ssize_t r = pread(fd, &data[o], e - o, (off_t)o);
-                        if (r <= 0) {
-                            shortr = true;
-                            return;
-                        }
-                        o += (size_t)r;
-                    }
-                });
-                if (shortr) {
-                    fclose(f);
-                    err = "short read on reference FASTA " + path;
-                    return false;
-                }
-                fseeko(f, sz, SEEK_SET);
-            }
-        }
-        char buf[1 << 16];
-        size_t k;
-        while ((k = fread(buf, 1, sizeof buf, f)) > 0) data.insert(data.end(), buf, buf + k);  // non-seekable input
-        fclose(f);
-        std::vector<size_t> hs;
-        const char *b = data.data(), *e = b + data.size();
-        for (const char *q = b; q < e && (q = (const char *)memchr(q, '>', (size_t)(e - q))); ++q)
-            if (q == b || q[-1] == '\n') hs.push_back((size_t)(q - b));
-        // names first (serially: the map's entries are made here, the last of a repeated name wins),
-        // then the bodies into the entries' strings (their storage reused across loads)
-        std::vector<std::string> names(hs.size());
-        std::vector<size_t> les(hs.size());
-        for (size_t c = 0; c < hs.size(); ++c) {
-            const size_t h = hs[c], stop = c + 1 < hs.size() ? hs[c + 1] : data.size();
-            size_t le = find_nl(h);
-            if (le == std::string::npos || le > stop) le = stop;
-            size_t ne = h + 1;
-            while (ne < le && data[ne] != ' ' && data[ne] != '\t' && data[ne] != '\r') ++ne;
-            names[c].assign(data.data() + h + 1, ne - h - 1);
-            les[c] = le;
-        }
-        std::unordered_map<std::string, size_t> last;
-        for (size_t c = 0; c < hs.size(); ++c) last[names[c]] = c;
-        for (auto it = seq.begin(); it != seq.end();)  // contigs of an earlier file that this one lacks
-            it = last.count(it->first) ? std::next(it) : seq.erase(it);
-        std::vector<std::string *> bodies(hs.size(), nullptr);
-        for (auto &kv : last) bodies[kv.second] = &seq[kv.first];
-        pool.run(hs.size(), [&](size_t c) {
-            if (!bodies[c]) return;  // a repeated name: a later entry holds it
-            const size_t stop = c + 1 < hs.size() ? hs[c + 1] : data.size(), le = les[c];
-            std::string &out = *bodies[c];
-            out.clear();
-            out.reserve(stop > le ? stop - le : 0);
-            size_t p = le + 1;
-            while (p < stop) {
-                size_t q = find_nl(p);
-                if (q == std::string::npos || q > stop) q = stop;
-                size_t qe = q;
-                if (qe > p && data[qe - 1] == '\r') --qe;
-                out.append(data.data() + p, qe - p);
-                p = q + 1;
-            }
-        });
-        if (seq.empty()) {
-            err = "no sequences in reference FASTA " + path;
-            return false;
-        }
-        return true;
-    }
-    const std::string *get(const std::string &name) const {
-        auto it = seq.find(name);
-        return it == seq.end() ? nullptr : &it->second;
-    }
-};
 
 // =====================================================================================  GenomeLoc
 struct GLoc {

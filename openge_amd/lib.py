@@ -108,6 +108,17 @@ class TargetsResult(C.Structure):
 TARGETS_TEXT = 1
 
 
+class CalmdOpts(C.Structure):
+    """Mirror of oge_calmd_opts (include/openge_hip.h)."""
+    _fields_ = [("threads", C.c_int32), ("flags", C.c_uint32)]
+
+
+class CalmdResult(C.Structure):
+    """Mirror of oge_calmd_result."""
+    FIELDS = ("records", "skipped", "no_reference", "nm_changed", "md_changed", "bytes_out")
+    _fields_ = [(k, C.c_uint64) for k in FIELDS]
+
+
 def _ref_table(refs) -> tuple[np.ndarray, bytes]:
     """[(name, length)] -> (lengths i32, the names NUL-terminated one after the other)"""
     return np.array([ln for _, ln in refs], np.int32), b"".join(nm.encode() + b"\0" for nm, _ in refs)
@@ -381,6 +392,10 @@ def lib() -> C.CDLL:
         "oge_targets_dev": (C.c_int, [vp, vp, vp, u64, i32, vp, C.c_char_p, u64, vp, vp, C.POINTER(vp), C.POINTER(vp)]),
         "oge_targets": (C.c_int, [vp, vp, u64, vp, u64, i32, vp, C.c_char_p, u64, vp, vp, vp, u64, vp, u64]),
         "oge_bam_targets_dev": (C.c_int, [vp, vp, u64, vp, vp, C.POINTER(vp), C.POINTER(vp)]),
+        "oge_calmd_opts_init": (None, [vp]),
+        "oge_calmd_dev": (C.c_int, [vp, vp, vp, u64, i32, C.c_char_p, u64, C.c_char_p, vp, vp, C.POINTER(vp), C.POINTER(vp)]),
+        "oge_calmd": (C.c_int, [vp, vp, u64, vp, u64, i32, C.c_char_p, u64, C.c_char_p, vp, vp, vp, u64, vp]),
+        "oge_bam_calmd_dev": (C.c_int, [vp, vp, u64, C.c_char_p, vp, vp, C.POINTER(vp), C.POINTER(vp)]),
         "oge_dup_metrics_dev": (C.c_int, [vp, vp, vp, u64, vp, i32, vp]),
         "oge_dup_metrics": (C.c_int, [vp, vp, u64, vp, u64, vp, i32, vp]),
         "oge_bam_dup_metrics_dev": (C.c_int, [vp, vp, u64, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(u64), C.POINTER(i32)]),
@@ -906,6 +921,52 @@ class Context:
             o, res, dt, dx = self._targets_opts(max_interval, gap), TargetsResult(), C.c_void_p(), C.c_void_p()
             check(lib().oge_bam_targets_dev(self.h, dz, nbytes, C.byref(o), C.byref(res), C.byref(dt), C.byref(dx)), self.h)
             return self._targets_out(res, dt, dx)
+        return self._with_file(data, run)
+
+    # ---- NM / MD tags (csrc/calmd.hip)
+    @staticmethod
+    def _calmd_opts(threads: int) -> CalmdOpts:
+        o = CalmdOpts()
+        lib().oge_calmd_opts_init(C.byref(o))
+        o.threads = threads
+        return o
+
+    def _calmd_out(self, res: CalmdResult, n: int, dr, do) -> tuple[dict, np.ndarray, np.ndarray]:
+        recs = np.frombuffer(self._fetch(dr.value or 0, res.bytes_out), np.uint8)
+        offs = np.frombuffer(self._fetch(do.value or 0, 8 * (n + 1)), np.uint64)
+        return {k: getattr(res, k) for k in CalmdResult.FIELDS}, recs, offs
+
+    def calmd_dev(self, d_recs, d_off, n: int, refs, fasta: str, threads: int = 0) -> tuple[dict, np.ndarray, np.ndarray]:
+        """oge_calmd_dev on device records; refs = [(name, length)], fasta = the reference's path -> (the counters of
+        oge_calmd_result, the new records as uint8, their n + 1 offsets as uint64)."""
+        _, names = _ref_table(refs)
+        o, res, dr, do = self._calmd_opts(threads), CalmdResult(), C.c_void_p(), C.c_void_p()
+        check(lib().oge_calmd_dev(self.h, d_recs, d_off, n, len(refs), names, len(names), fasta.encode(), C.byref(o), C.byref(res),
+                                  C.byref(dr), C.byref(do)), self.h)
+        return self._calmd_out(res, n, dr, do)
+
+    def calmd(self, recs: np.ndarray, offs: np.ndarray, n: int, refs, fasta: str, threads: int = 0) -> tuple[dict, np.ndarray, np.ndarray]:
+        """oge_calmd: the same from host buffers (a sizing call, then the call that copies the records)."""
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        _, names = _ref_table(refs)
+        o, res = self._calmd_opts(threads), CalmdResult()
+        out_off = np.zeros(n + 1, np.uint64)
+        args = (self.h, _ptr(recs), max(recs.nbytes - 16, 0), _ptr(offs), n, len(refs), names, len(names), fasta.encode(), C.byref(o),
+                C.byref(res))
+        rc = lib().oge_calmd(*args, None, 0, _ptr(out_off))
+        if not (rc == -3 and res.bytes_out):  # OGE_ERR_LIMIT with the size: the sizing call
+            check(rc, self.h)
+        out = np.zeros(max(res.bytes_out, 1), np.uint8)
+        if rc:
+            check(lib().oge_calmd(*args, _ptr(out), res.bytes_out, _ptr(out_off)), self.h)
+        return {k: getattr(res, k) for k in CalmdResult.FIELDS}, out[:res.bytes_out], out_off
+
+    def bam_calmd(self, data: bytes, fasta: str, threads: int = 0) -> tuple[dict, np.ndarray, np.ndarray]:
+        """`openge calmd` of a whole BAM file (oge_bam_calmd_dev on a copy of the file in HBM)."""
+        def run(dz, nbytes):
+            o, res, dr, do = self._calmd_opts(threads), CalmdResult(), C.c_void_p(), C.c_void_p()
+            check(lib().oge_bam_calmd_dev(self.h, dz, nbytes, fasta.encode(), C.byref(o), C.byref(res), C.byref(dr), C.byref(do)), self.h)
+            return self._calmd_out(res, res.records, dr, do)
         return self._with_file(data, run)
 
     # ---- duplication metrics (csrc/dupmetrics.hip)
